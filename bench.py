@@ -103,7 +103,12 @@ def main():
     ap.add_argument("--no_graph", action="store_true", help="launch the rollout eagerly instead of replaying a hipGraph")
     ap.add_argument("--cpu_seconds", type=float, default=12.0)
     ap.add_argument("--launch_check", action="store_true", help="plumbing check without a GPU: launch the ranks, rendezvous over gloo, print one line, exit")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (the networks' parameters and buffers, the rollout storage) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB in all (larger arrays as a fixed seeded sample; DIR/manifest.json says which)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_self_launch(args.gpus))
 
@@ -192,6 +197,8 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:                # before the kernel timings and rollouts below, which overwrite the storage
+        dump_outputs(args.dump_outputs, timed_outputs(runner))
     # live timing of the fused env-step kernel: HIP events around single launches on the launch stream, same process,
     # same env state, right after the timed region (inside it the 24 steps of a rollout replay as ONE hipGraph launch,
     # which leaves no place for per-kernel events; profiles/ holds the rocprofv3 per-kernel average of the same command)
@@ -335,6 +342,62 @@ def _stamped_traffic(g, num_envs, name="env_step_traffic.json"):
     return d.get("hbm_bytes_per_launch"), f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes on kernel sources {d['kernel_source_hash']} (tools/final_measure.sh)"
 
 
+DUMP_BUDGET_BYTES = 60 << 20          # --dump-outputs: the arrays' data; the .npy headers and the manifest stay far below the rest of 64 MB
+
+
+def timed_outputs(runner, storage=True):
+    """what a caller of runner.learn() holds after the last timed iteration: the parameters and buffers of the networks it trains and the
+    rollout storage that iteration filled (observations, actions, rewards, values, returns, advantages, ...; not with storage=False: the
+    depth student's iteration does not fill it).  Name -> tensor."""
+    import torch
+    alg, out = runner.alg, {}
+    for mod in ("actor_critic", "estimator", "disc", "depth_encoder", "depth_actor"):
+        m = getattr(alg, mod, None)
+        if isinstance(m, torch.nn.Module):
+            out.update((f"{mod}.{k}", v) for k, v in m.state_dict().items() if torch.is_tensor(v))
+    for k, v in (vars(alg.storage).items() if storage else ()):
+        if torch.is_tensor(v) and not k.startswith("_") and v.dim() and not any(v is w for w in out.values()):      # privileged rows may alias the actor's
+            out["storage." + k] = v
+    return out
+
+
+def dump_outputs(path, tensors):
+    """writes every tensor as <path>/<name>.npy: float64 stays float64, integer tensors become float64, the rest float32.  Within
+    DUMP_BUDGET_BYTES: the arrays in ascending size each get an equal share of what the smaller ones left; an array over its share is
+    written as a sample of its elements -- flat indices drawn from a generator seeded by the name (so the same in every run of the same
+    shapes), sorted, duplicates dropped.  <path>/manifest.json lists shape, dtype and, for samples, the seed and element count."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+
+    def dtype(t):
+        return np.float64 if t.dtype in (torch.float64, torch.int64, torch.int32) else np.float32
+
+    items = sorted(tensors.items(), key=lambda kv: (kv[1].numel() * np.dtype(dtype(kv[1])).itemsize, kv[0]))
+    left, manifest = DUMP_BUDGET_BYTES, {}
+    for i, (name, t) in enumerate(items):
+        dt = dtype(t)
+        share = left // (len(items) - i)
+        entry = {"shape": list(t.shape), "dtype": np.dtype(dt).name}
+        t = t.detach()
+        if t.numel() * np.dtype(dt).itemsize <= share:
+            arr = t.cpu().numpy().astype(dt)
+        else:
+            seed = zlib.crc32(name.encode())
+            draws = share // np.dtype(dt).itemsize
+            flat = np.unique(np.random.default_rng(seed).integers(0, t.numel(), draws))
+            idx = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(t.device) for a in np.unravel_index(flat, tuple(t.shape)))
+            arr = t[idx].cpu().numpy().astype(dt)
+            entry["sample"] = {"elements": int(arr.size), "of": int(t.numel()), "seed": seed, "draws": int(draws),
+                               "index": "np.unique(np.random.default_rng(seed).integers(0, of, draws)), C-order flat indices"}
+        np.save(os.path.join(path, name + ".npy"), arr)
+        left -= arr.nbytes
+        manifest[name] = entry
+    with open(os.path.join(path, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
+
+
 def _barrier_sync(world):
     import torch
     import torch.distributed as dist
@@ -413,6 +476,8 @@ def bench_tsc(args, world, rank, local_rank, dev):
         print("per-iteration ms:", " ".join(f"{v:.1f}" for v in iter_ms), file=sys.stderr)
     _barrier_sync(world)
     dt = _max_over_ranks(time.perf_counter() - t0, world, dev)
+    if args.dump_outputs and rank == 0:                # before the rollouts below, which overwrite the storage
+        dump_outputs(args.dump_outputs, timed_outputs(runner, storage=not args.vision))
     # the two phases of an iteration, measured apart AFTER the timed region between device syncs (inside it the host never waits for the
     # GPU -- a recorded rollout returns to the host in ~1 ms -- so the runner's own host clocks are not phase times)
     coll_s = None
