@@ -1149,7 +1149,7 @@ class ClipAdamPair:
         stride = (C.c_int64 * n)(*[(e[3] if e is not None else 0) for e in pend])
         parts = (C.c_int32 * n)(*[(e[2] if e is not None else 0) for e in pend])
         pair = _capi.QaAdamPair(ta["n"], ta["num_chunks"], pb["lr_dev"].data_ptr(), b.max_norm, kl.data_ptr() if kl is not None else None,
-                                float(desired_kl), float(factor), float(lr_min), float(lr_max))
+                                float(desired_kl) if kl is not None else 0.0, float(factor), float(lr_min), float(lr_max))
         lib = _capi.load_library()
         params = pa["params"] + pb["params"]
         rc = lib.qa_clip_adam_pair_step(_ptr(m["params"]), (C.c_void_p * n)(*ptrs), _ptr(m["exp_avg"]), _ptr(m["exp_avg_sq"]), _ptr(m["steps"]), m["n"],

@@ -861,7 +861,10 @@ class SSInfoGAIL:
             c_all = logits_all if logits_in_kernel else torch.softmax(logits_all, -1)               # (the objective kernel clamps)
             if self.disc_normalizer is not None and self.grad_sync is None:
                 # the input normaliser folds in this step's batches (gail.py:524-528, at the end of the step there): nothing else in the step reads or
-                # writes its moments, so the fold runs beside the step instead of behind it
+                # writes its moments, so the fold runs beside the step instead of behind it.  The moments' readers: disc_prepare / qa_disc_sample_prepare
+                # at the start of the NEXT step (x_all was normalised before this fold), the data-parallel branch (excluded: grad_sync is None here),
+                # predict_disc_reward in the rollout.  dchain.backward() joins the fold's side stream (QA_TRAIN_CHAIN_SIDES=1) before the optimiser
+                # steps.  tests/test_gpu_learner_golden.py holds three consecutive steps of a non-trivial normaliser to the reference's order
                 nb_ = [policy_state, expert_lb, expert_ulb]          # (slices of the prepared matrix, in the order the reference folds them)
                 dchain.beside(lambda: self.disc_normalizer.update_torch(nb_))
                 normaliser_done = True

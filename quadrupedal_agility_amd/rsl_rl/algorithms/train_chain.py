@@ -442,6 +442,8 @@ class DiscTrainChain:
         """gradients at the three heads' outputs (R rows) + the penalty's coefficient c (loss term c * mean_U |g|^2) -> `.grad` of the 10 parameters.
         finish=False leaves the six products IN PARTS and returns {parameter: record} for fused.StackedAdam.step, whose launch adds the parts (the
         penalty's with the factor a), writes `.grad` and steps the optimisers: no reduction launch, no multi-tensor adds here."""
+        if self.sides:
+            self.sides.join()        # what `beside()` forked ends here: before the optimiser steps, and before a recording's end
         k0, w1, w2, nh = self.dims
         l1, l2 = self.disc._relu_trunk()
         gin = self.gin

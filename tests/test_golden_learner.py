@@ -192,3 +192,27 @@ def test_only_networks_whose_backward_we_reduce_ourselves_are_recorded(fx):
     alg.actor_critic.actor_trunk[1] = torch.nn.ELU()
     alg.disc_loss_function = "WassersteinLoss"
     assert not alg._recordable_networks()
+
+
+# ------------------------------------------------------------------ consecutive steps (learner_steps.pt): gradients by value, not sign
+def test_mirror_ppo_first_step_gradients_equal_the_references():
+    """every pre-clip gradient of the reference's step 1, element-wise, and clip_grad_norm_'s two global norms"""
+    from tests.test_gpu_learner_golden import check_ppo_grads, first_half_grads, load_fixture
+    fx = load_fixture()
+    grads, _ = first_half_grads(fx, "cpu")
+    check_ppo_grads(grads, fx["ppo"][0]["grads"], fx["ppo"][0]["grad_norm"], "cpu")
+
+
+@pytest.mark.parametrize("key,over", [("ppo", {}), ("ppo_kl_none", dict(desired_kl=None)), ("ppo_fixed", dict(schedule="fixed"))])
+def test_mirror_consecutive_ppo_steps_equal_the_references(key, over):
+    from tests.test_gpu_learner_golden import assert_steps, load_fixture, run_ppo_steps
+    errs, _ = run_ppo_steps(load_fixture(), "cpu", key, **over)
+    assert_steps("cpu_" + key, errs, names=("loss", "w_abs", "w_sum"))
+
+
+def test_mirror_three_discriminator_steps_equal_the_references():
+    from tests.test_gpu_learner_golden import assert_steps, check_disc_grads, load_fixture, run_disc_steps
+    fx = load_fixture()
+    errs, grads1, _ = run_disc_steps(fx, "cpu")
+    check_disc_grads(grads1, fx["disc"][0]["grads"], "cpu")
+    assert_steps("cpu_disc", errs)

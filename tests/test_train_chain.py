@@ -60,6 +60,50 @@ def _check_grads(params_ref, params_got, rtol, tag):
         assert err <= rtol * scale, (tag, name, err, scale)
 
 
+# float64 references: per tensor, the relative L2 error and the largest element error over the tensor's RMS (measured maximum over every case on
+# the MI355X in brackets).  A reference with ONE 16-row tile's contribution removed must fall outside them (_assert_tile_rejected).
+F64_REL = 1e-5            # [2.05e-6: PPO chain, 3072 rows]  (one 16-row tile dropped: 2.5e-1 at 3072 rows, 2.9e-2 at 24,576)
+F64_ELEM = 1e-4           # [2.17e-5: whole autograd step, 8193 rows]
+
+
+def _double(*mods):
+    import copy
+    return [copy.deepcopy(m).double() for m in mods]
+
+
+def _f64_errors(named64, got):
+    """{name: (|g - r|_2 / |r|_2, max |g - r| / rms(r))} for every parameter the float64 reference has a gradient for"""
+    out = {}
+    for (name, p), q in zip(named64, got):
+        if p.grad is None:
+            continue
+        r, g = p.grad, q.grad.detach().double().cpu()
+        rn = float(r.norm())
+        out[name] = (float((g - r).norm()) / rn, float((g - r).abs().max()) / (rn / r.numel() ** 0.5))
+    return out
+
+
+def _check_f64(named64, got, tag):
+    errs = _f64_errors(named64, got)
+    print("MEASURED", tag, "f64_rel=%.3e f64_elem=%.3e" % (max(e[0] for e in errs.values()), max(e[1] for e in errs.values())))
+    bad = {n: e for n, e in errs.items() if not (e[0] <= F64_REL and e[1] <= F64_ELEM)}
+    assert not bad, (tag, bad)
+
+
+def _assert_tile_rejected(named64, got, tag):
+    """the bounds have teeth: against a reference without one 16-row tile, some tensor is out of bounds"""
+    errs = _f64_errors(named64, got)
+    worst = max(e[0] for e in errs.values())
+    print("MEASURED", tag, "tile_dropped_rel=%.3e" % worst)
+    assert any(e[0] > F64_REL or e[1] > F64_ELEM for e in errs.values()), (tag, worst)
+
+
+def _drop_tile(t, t0=16):
+    t = t.clone()
+    t[t0:t0 + 16] = 0
+    return t
+
+
 def test_chain_programs_equal_autograd_through_the_oracle_twins():
     from quadrupedal_agility_amd.rsl_rl.algorithms import train_chain
     lib = load_oracle()
@@ -106,14 +150,17 @@ def test_describe_declines_what_the_programs_do_not_cover():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("rows", [48, 3072, 6144])
+@pytest.mark.parametrize("rows", [48, 3072, 6144, 8192])
 def test_hip_chain_equals_autograd(rows):
     from quadrupedal_agility_amd.rsl_rl.algorithms import fused, train_chain
     ac, est, n_obs = _modules(3)
     ac_r, est_r, _ = _modules(3)
+    ac64, est64 = _double(ac_r, est_r)
     ac, est = ac.cuda(), est.cuda()
     obs, g_est, dmu, dvalue, g_priv = _inputs(rows, n_obs, seed=rows)
     e_ref, mu_ref, v_ref, p_ref = _reference(ac_r, est_r, obs, g_est, dmu, dvalue, g_priv)
+    _reference(ac64, est64, *[t.double() for t in (obs, g_est, dmu, dvalue, g_priv)])
+    ref64 = list(ac64.named_parameters()) + list(est64.named_parameters())
     chain = train_chain.PpoTrainChain.describe(ac, est, rows)
     assert chain is not None
     chain.pack()
@@ -127,6 +174,11 @@ def test_hip_chain_equals_autograd(rows):
     chain.backward(*dv[1:], defer=False)
     torch.cuda.synchronize()
     _check_grads(ref, got, 3e-4, "finished")
+    _check_f64(ref64, got, f"ppo chain {rows} rows")
+    if rows == 3072:
+        _reference(ac64, est64, obs.double(), *[_drop_tile(t.double()) for t in (g_est, dmu, dvalue, g_priv)])
+        _assert_tile_rejected(list(ac64.named_parameters()) + list(est64.named_parameters()), got, f"ppo chain {rows} rows")
+        _reference(ac64, est64, *[t.double() for t in (obs, g_est, dmu, dvalue, g_priv)])
     first = [p.grad.clone() if p.grad is not None else None for p in got]
     # in parts: nothing finished until somebody asks
     for p in got:
@@ -138,9 +190,74 @@ def test_hip_chain_equals_autograd(rows):
     assert fused.pending_grads() == 0
     torch.cuda.synchronize()
     _check_grads(ref, got, 3e-4, "parts")
+    _check_f64(ref64, got, f"ppo chain {rows} rows, in parts")
     for a, b in zip(first, got):          # the same partial products, added by either finish (qa_slab_reduce / qa_grad_reduce: fixed orders, not the same one)
         if a is not None:
             assert torch.allclose(a, b.grad, rtol=1e-5, atol=1e-6 * float(a.abs().max() + 1e-30))
+
+
+def _whole_step_sample(ac64, rows, seed):
+    """a PPO minibatch whose ratios straddle the clip range: old policy = the current one nudged, actions drawn from it"""
+    from torch.distributions import Normal
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s_: torch.randn(*s_, generator=g)
+    obs = r(rows, 671) * 0.5
+    obs[:, 666:671] = torch.nn.functional.one_hot(torch.randint(0, 5, (rows,), generator=g), 5).float()
+    with torch.no_grad():
+        mu = ac64._actor_mean(obs.double(), False).float()
+    old_mu = mu + 0.05 * r(rows, 12)
+    old_sigma = torch.full((rows, 12), 0.95)
+    actions = old_mu + old_sigma * r(rows, 12)
+    old_logp = Normal(old_mu, old_sigma).log_prob(actions).sum(-1, keepdim=True)
+    return [obs, actions, r(rows, 1), r(rows, 1), r(rows, 1), old_logp, old_mu, old_sigma]
+
+
+def _whole_step_reference(alg, coef, ac64, est64, s, keep=None):
+    """float64 autograd of what _ac_forward_backward_direct composes: fused.ppo_loss_reference + coef x the privileged-latent regulariser on
+    the actor-critic, the estimator's regression on the estimator.  `keep`: only those rows, each loss still divided by ALL rows (= the other
+    rows' loss weights zeroed)"""
+    from quadrupedal_agility_amd.rsl_rl.algorithms import fused
+    rows = s[0].shape[0]
+    obs, actions, tv, adv, ret, old_logp, old_mu, old_sigma = [t.double()[keep] if keep is not None else t.double() for t in s]
+    w = obs.shape[0] / rows
+    for p in list(ac64.parameters()) + list(est64.parameters()):
+        p.grad = None
+    a = alg.num_prop; b = a + alg.num_explicit; c = b + alg.num_latent; d = c + alg.num_hist * alg.num_prop
+    mu, value = ac64._actor_mean(obs, False), ac64.evaluate(obs)
+    ppo, _ = fused.ppo_loss_reference(mu, ac64.std, value, actions, old_logp, old_mu, old_sigma, adv, ret, tv, clip=alg.clip_param,
+                                      c_surr=alg.surrogate_loss_coef, c_value=alg.value_loss_coef, c_bound=alg.bounds_loss_coef,
+                                      c_entropy=alg.entropy_coef, clipped_value=alg.use_clipped_value_loss)
+    priv = ac64.infer_priv_latent(obs[:, b:c])
+    with torch.no_grad():
+        hist = ac64.infer_hist_latent(obs[:, c:d])
+    (w * (ppo + coef * (priv - hist).norm(p=2, dim=1).mean())).backward()
+    (w * (est64(obs[:, :a]) - obs[:, a:b]).pow(2).mean()).backward()
+    return list(ac64.named_parameters()) + list(est64.named_parameters())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows", [8193, 24576])
+def test_whole_autograd_step_equals_float64_autograd(rows):
+    """above MAX_ROWS the headline's step: _ac_forward_backward's three-stream autograd path (qa_ppo_loss, qa_narrow_wgrad, qa_pair_losses with the
+    recorded step's device coefficient, hipBLASLt) -- every finished gradient against float64 autograd of the same objective"""
+    import copy
+    from quadrupedal_agility_amd.rsl_rl.algorithms import fused
+    from tests.test_gpu_learner_golden import build, load_fixture
+    env, alg = build(load_fixture(), "cuda")
+    assert alg._train_chain_rows(rows) is None
+    coef = alg._priv_reg_coef_now()
+    alg._priv_reg_coef_now = lambda: torch.tensor(coef, dtype=torch.float32, device="cuda")
+    ac64, est64 = copy.deepcopy(alg.actor_critic).cpu().double(), copy.deepcopy(alg.estimator).cpu().double()
+    s = _whole_step_sample(ac64, rows, rows)
+    dv = [t.cuda() for t in s]
+    alg._ac_forward_backward((dv[0], dv[0], *dv[1:], (None, None), None))
+    fused.flush_pending_grads()
+    torch.cuda.synchronize()
+    got = list(alg.actor_critic.parameters()) + list(alg.estimator.parameters())
+    _check_f64(_whole_step_reference(alg, coef, ac64, est64, s), got, f"whole step {rows} rows")
+    if rows == 24576:
+        keep = torch.cat([torch.arange(0, 16), torch.arange(32, rows)])
+        _assert_tile_rejected(_whole_step_reference(alg, coef, ac64, est64, s, keep), got, f"whole step {rows} rows")
 
 
 @pytest.mark.gpu
@@ -240,9 +357,11 @@ def test_discriminator_chain_programs_equal_double_backward_through_the_oracle_t
 def test_hip_discriminator_chain_equals_double_backward(mb):
     from quadrupedal_agility_amd.rsl_rl.algorithms import train_chain
     disc_r, disc = _disc(5), _disc(5).cuda()
+    (disc64,) = _double(disc_r)
     rows, n_u, c_gp = 3 * mb, mb, 0.2
     x, g_d, g_eps, g_l = _disc_inputs(rows, mb)
     d_ref, e_ref, l_ref, g_ref = _disc_reference(disc_r, x, n_u, g_d, g_eps, g_l, c_gp)
+    _disc_reference(disc64, x.double(), n_u, g_d.double(), g_eps.double(), g_l.double(), c_gp)
     chain = train_chain.DiscTrainChain.describe(disc, rows, n_u)
     assert chain is not None
     chain.pack()
@@ -254,6 +373,7 @@ def test_hip_discriminator_chain_equals_double_backward(mb):
     chain.backward(g_d.cuda(), g_eps.cuda(), g_l.cuda(), c_gp)
     torch.cuda.synchronize()
     _check_grads(list(disc_r.named_parameters()), list(disc.parameters()), 3e-4, "disc")
+    _check_f64(list(disc64.named_parameters()), list(disc.parameters()), f"disc chain mb {mb}")
 
 
 @pytest.mark.gpu
@@ -479,17 +599,20 @@ def test_task_level_chain_programs_equal_autograd_through_the_oracle_twins():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("rows", [40, 6144])
+@pytest.mark.parametrize("rows", [40, 48, 3072, 6144, 8192])
 def test_hip_task_level_chain_equals_autograd(rows):
     from tests.test_policy_chain import tsc_modules
     from quadrupedal_agility_amd.rsl_rl.algorithms import fused, train_chain
     ac_r, est_r, n_obs = tsc_modules(6)
+    ac64, est64 = _double(ac_r, est_r)
     ac, est, _ = tsc_modules(6)
     ac, est = ac.cuda(), est.cuda()
     chain = train_chain.TscTrainChain.describe(ac, est, rows, 57)
     assert chain is not None
     ins = _tsc_inputs(rows, n_obs, chain.dims["nd"], chain.dims["nc"], seed=rows)
     refs = _tsc_reference(ac_r, est_r, *ins)
+    _tsc_reference(ac64, est64, *[t.double() for t in ins])
+    ref64 = list(ac64.named_parameters()) + list(est64.named_parameters())
     dv = [x.cuda() for x in ins]
     chain.pack()
     outs = chain.forward(dv[0])
@@ -501,6 +624,7 @@ def test_hip_task_level_chain_equals_autograd(rows):
     chain.backward(*dv[1:], defer=False)
     torch.cuda.synchronize()
     _check_grads(ref, got, 3e-4, "finished")
+    _check_f64(ref64, got, f"task-level chain {rows} rows")
     for p in got:
         p.grad = None
     chain.forward(dv[0])
@@ -509,3 +633,4 @@ def test_hip_task_level_chain_equals_autograd(rows):
     fused.flush_pending_grads()
     torch.cuda.synchronize()
     _check_grads(ref, got, 3e-4, "parts")
+    _check_f64(ref64, got, f"task-level chain {rows} rows, in parts")

@@ -15,6 +15,15 @@ Fixtures:
   learner.pt             ActorCritic / Estimator / Discriminator forward, predict_disc_reward,
                          one update_actor_critic step and one update_ss_info_gail step (losses and
                          post-step weights) of SSInfoGAIL (gail.py:328-541)
+  learner_steps.pt       consecutive steps of SSInfoGAIL from learner.pt's init (stored there, not here): PPO steps on three 96-row samples and
+                         a 37-row one (adaptive KL), two with desired_kl=None, two with schedule="fixed"; three update_ss_info_gail steps
+                         with a non-trivial normaliser and info_max_coef_on = 0.3.  Per step the losses, lr_ac, clip_grad_norm_'s global
+                         norms, the normaliser / prior and the weights (compact); for step 1 every parameter's gradient before clipping
+                         (PPO: torch.nn.utils.clip_grad_norm_ wrapped here; discriminator: .grad as the first optimiser step sees it), in
+                         full up to 4 k elements, else a stride-37 sample + L2 norm + sum; weights as stride-257 samples + sums, packed per snapshot.  The
+                         inputs are not stored: tests/learner_steps_inputs.py draws them from a seed, the fixture keeps their SHA-256.
+                         Steps 2+ pin gradient magnitudes (Adam's m / sqrt(v) is sign(g) at step 1 only).
+                         `python tools/gen_golden.py learner_steps` writes it alone
   mocap.npz              MotionLoader.reorder and get_full_frame_at_time_batch on a labelled clip
 
 Random draws: the reference mixes torch / numpy RNGs that cannot be matched by a counter-based
@@ -268,11 +277,10 @@ def compact(sd, stride=97):
             for k, v in sd.items()}
 
 
-def gen_learner(RefCfg, RefAlgoCfg):
-    """Reference networks + one PPO step + one discriminator step with everything seeded/fixed."""
+def _ref_learner_parts(RefCfg, RefAlgoCfg):
+    """The reference's networks and disc normaliser with learner.pt's seeds: (tcfg, env, ac, est, norm, disc, init state dicts)."""
     from legged_gym.utils.helpers import class_to_dict
     from rsl_rl.algorithms.discriminator import Discriminator
-    from rsl_rl.algorithms.gail import SSInfoGAIL
     from rsl_rl.modules import ActorCritic, Estimator
     from rsl_rl.utils.utils import Normalizer
     torch.manual_seed(123)
@@ -289,6 +297,13 @@ def gen_learner(RefCfg, RefAlgoCfg):
     disc = Discriminator(env, 98, 49, 5, 0.02, "MSELoss", None, 1.0, 0.01, 0.2, 0.2, 2, 2, 0.0, [512, 256], "cpu")
     init = {"actor_critic": {k: v.clone() for k, v in ac.state_dict().items()}, "estimator": {k: v.clone() for k, v in est.state_dict().items()},
             "disc": {k: v.clone() for k, v in disc.state_dict().items()}}
+    return tcfg, env, ac, est, norm, disc, init
+
+
+def gen_learner(RefCfg, RefAlgoCfg):
+    """Reference networks + one PPO step + one discriminator step with everything seeded/fixed."""
+    from rsl_rl.algorithms.gail import SSInfoGAIL
+    tcfg, env, ac, est, norm, disc, init = _ref_learner_parts(RefCfg, RefAlgoCfg)
     B = 96
     g = torch.Generator().manual_seed(7)
     obs = torch.randn(B, 671, generator=g) * 0.5
@@ -345,6 +360,105 @@ def gen_learner(RefCfg, RefAlgoCfg):
     torch.save(fx, os.path.join(GOLD, "learner.pt"))
 
 
+def compact_grad(t, full_max=4096, stride=37):
+    """A pre-clip gradient: in full up to 4 k elements, else a stride-37 sample + its L2 norm and sum (fp64)."""
+    t = t.detach()
+    if t.numel() <= full_max:
+        return {"full": t.clone()}
+    return {"sample": t.flatten()[::stride].clone(), "stride": stride, "norm": t.double().norm().item(), "sum": t.double().sum().item()}
+
+
+WSTRIDE = 257       # learner_steps.pt's weight samples: sparser than learner.pt's 97 (fourteen snapshots, and the file must stay small)
+
+
+def compact_packed(sd, stride=WSTRIDE):
+    """compact() as one record per snapshot: every tensor's stride-`stride` sample concatenated in state-dict order, and the fp64 sums"""
+    return {"names": list(sd), "sample": torch.cat([v.flatten()[::stride] for v in sd.values()]).clone(),
+            "sum": torch.tensor([v.double().sum().item() for v in sd.values()], dtype=torch.float64)}
+
+
+def gen_learner_steps(RefCfg, RefAlgoCfg):
+    """Consecutive learner steps of the reference's SSInfoGAIL from learner.pt's init weights and normaliser: what pins the GPU learner's
+    gradients by value (one Adam step from fresh state moves every weight by lr * sign(g) and hides the magnitudes)."""
+    from rsl_rl.algorithms.gail import SSInfoGAIL
+    tcfg, env, ac, est, norm, disc, init = _ref_learner_parts(RefCfg, RefAlgoCfg)
+    norm0 = {"mean": norm.mean.copy(), "var": norm.var.copy(), "count": norm.count}
+    names = {id(p): n for n, p in list(ac.named_parameters()) + [("estimator." + n, p) for n, p in est.named_parameters()]}
+    calls = []
+    clip = torch.nn.utils.clip_grad_norm_
+
+    def clip_recorded(parameters, max_norm, *a, **kw):          # the reference calls nn.utils.clip_grad_norm_ at run time: wrapped here, not edited there
+        params = list(parameters)
+        pre = {names[id(p)]: p.grad.detach().clone() for p in params if p.grad is not None}
+        n = clip(params, max_norm, *a, **kw)
+        calls.append((pre, float(n)))
+        return n
+    torch.nn.utils.clip_grad_norm_ = clip_recorded
+
+    def fresh(**alg_over):
+        ac.load_state_dict(init["actor_critic"]); est.load_state_dict(init["estimator"]); disc.load_state_dict(init["disc"])
+        for p in list(ac.parameters()) + list(est.parameters()) + list(disc.parameters()):
+            p.grad = None
+        norm.mean, norm.var, norm.count = norm0["mean"].copy(), norm0["var"].copy(), norm0["count"]
+        env.prior_parameters = torch.ones(5) / 5
+        acfg = dict(tcfg["algorithm"], **alg_over)
+        alg = SSInfoGAIL(env, ac, disc, est, tcfg["estimator"], types.SimpleNamespace(), norm, 2, 2, 49, 0.0, device="cpu",
+                         min_std=torch.full((12,), 0.05), **acfg)
+        alg.priv_reg_counter = 1500
+        return alg
+
+    def ppo_steps(alg, samples, grads_of_first):
+        out = []
+        for i, smp in enumerate(samples):
+            del calls[:]
+            losses = alg.update_actor_critic(tuple(smp) + ((None, None), None))
+            (pre_e, n_e), (pre_ac, n_ac) = calls
+            st = {"losses": [l.detach().clone() if l.dim() == 0 else l.detach().mean().clone() for l in losses], "lr_after": alg.lr_ac,
+                  "grad_norm": {"estimator": n_e, "actor_critic": n_ac},
+                  "after": {"actor_critic": compact_packed(ac.state_dict()), "estimator": compact_packed(est.state_dict())}}
+            if i == 0 and grads_of_first:
+                st["grads"] = {k: compact_grad(v) for k, v in {**pre_e, **pre_ac}.items()}
+            out.append(st)
+        return out
+
+    from tests.learner_steps_inputs import digest, samples
+    ppo_in, disc_in = samples()                 # drawn from a seed on both sides: the fixture keeps their digest, not the tensors
+    ppo_samples = [[s_[0], s_[0]] + s_[1:] for s_ in ppo_in]
+    disc_samples = [(d["policy"], d["lb"], d["ulb"]) for d in disc_in]
+    ref = torch.load(os.path.join(GOLD, "learner.pt"), weights_only=False)          # the init is learner.pt's (not stored twice)
+    for part in init:
+        assert all(torch.equal(v, ref["init"][part][k]) for k, v in init[part].items()), part
+    assert all(np.array_equal(norm0[k], ref["normalizer"][k]) for k in ("mean", "var")) and norm0["count"] == ref["normalizer"]["count"]
+    fx = {"policy_cfg": tcfg["policy"], "alg_cfg": tcfg["algorithm"], "estimator_cfg": tcfg["estimator"],
+          "task_obs_weight": 0.7, "priv_reg_counter": 1500, "inputs_sha256": digest(ppo_in, disc_in), "weight_stride": WSTRIDE}
+    # ---- PPO: three 96-row steps, then a 37-row one (adaptive KL schedule, the config's)
+    fx["ppo"] = ppo_steps(fresh(), ppo_samples, True)
+    # ---- the non-adaptive schedules, two steps each
+    fx["ppo_kl_none"] = ppo_steps(fresh(desired_kl=None), ppo_samples[:2], False)       # (step 1's gradients: fx["ppo"][0]'s)
+    fx["ppo_fixed"] = ppo_steps(fresh(schedule="fixed"), ppo_samples[:2], False)
+    torch.nn.utils.clip_grad_norm_ = clip
+    # ---- discriminator: three steps, non-trivial normaliser, information maximisation on
+    alg = fresh()
+    alg.info_max_coef_on = 0.3
+    dnames = {id(p): n for n, p in disc.named_parameters()}
+    pre = []
+    step_d = alg.optim_d.step
+
+    def step_d_recorded(*a, **kw):        # the first of the three optimiser steps: every parameter's .grad is the whole loss's
+        pre.append({dnames[id(p)]: p.grad.detach().clone() for p in disc.parameters() if p.grad is not None})
+        return step_d(*a, **kw)
+    alg.optim_d.step = step_d_recorded
+    fx["disc"] = []
+    for i, (pol, lb, ulb) in enumerate(disc_samples):
+        dl = alg.update_ss_info_gail(pol, lb, ulb)
+        st = {"losses": [l.detach().clone() for l in dl], "prior_after": env.prior_parameters.clone(), "after": compact_packed(disc.state_dict()),
+              "normalizer_after": {"mean": norm.mean.copy(), "var": norm.var.copy(), "count": norm.count}}
+        if i == 0:
+            st["grads"] = {k: compact_grad(v) for k, v in pre[0].items()}
+        fx["disc"].append(st)
+    torch.save(fx, os.path.join(GOLD, "learner_steps.pt"))
+
+
 def gen_mocap():
     """The reference's reorder + batched frame blending on one labelled clip (input frames are a data file of the
     reference's dataset, truncated to 40 frames)."""
@@ -370,13 +484,15 @@ def gen_mocap():
 def _main():
     os.makedirs(GOLD, exist_ok=True)
     ref_lr, RefCfg, RefAlgoCfg = import_reference()
-    which = sys.argv[1:] or ["env", "gae", "learner", "mocap", "heights", "noise"]
+    which = sys.argv[1:] or ["env", "gae", "learner", "learner_steps", "mocap", "heights", "noise"]
     if "env" in which:
         gen_env(ref_lr, RefCfg)
     if "gae" in which:
         gen_gae()
     if "learner" in which:
         gen_learner(RefCfg, RefAlgoCfg)
+    if "learner_steps" in which:
+        gen_learner_steps(RefCfg, RefAlgoCfg)
     if "mocap" in which:
         gen_mocap()
     if "heights" in which:
