@@ -9,8 +9,13 @@ skipped inside the timed region.  value = num_envs x 24 x steps x n_gpus / wall 
   python bench.py --gpus 1 --steps 10 --warmup 3
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Extra objects on the JSON line: `roofline` (fused env-step kernel vs HBM, timed live with events on
-the launch stream) and `cpu_baseline` (the CPU oracle's env step on the host cores, bounded sample).
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line: the
+headline and what follows from the timed region alone.  --full also measures, after the timed region: the
+rollout / update split, `roofline` and `policy_roofline` (the fused env-step and policy kernels, timed live
+with events on the launch stream) and `cpu_baseline` (the CPU oracle's env step and whole torch-CPU
+iterations on the host cores, bounded samples; not with --no_cpu_baseline).
+
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
 """
 import argparse
 import json
@@ -99,9 +104,12 @@ def main():
     ap.add_argument("--vision", action="store_true", help="with --tsc: the depth student (BASELINE configs[4]: --use_camera, 4096 envs in total)")
     ap.add_argument("--tsc", action="store_true", help="BASELINE config 4: TSC teacher on the agility course (two-level rollout, hybrid PPO); "
                     "--num_envs is per GPU (8192 over 8 GPUs = 1024 per GPU)")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the rollout / update split, the env-side and policy kernels against their rooflines and, "
+                         "on one GPU, the CPU baseline (a minute or more); a plain run reports the timed steps alone")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no_graph", action="store_true", help="launch the rollout eagerly instead of replaying a hipGraph")
-    ap.add_argument("--cpu_seconds", type=float, default=12.0)
+    ap.add_argument("--cpu_seconds", type=float, default=12.0, help="with --full: the CPU baseline's budget for its rollout-only legs")
     ap.add_argument("--launch_check", action="store_true", help="plumbing check without a GPU: launch the ranks, rendezvous over gloo, print one line, exit")
     ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR",
                     help="after the timed steps, write what the last one computed (the networks' parameters and buffers, the rollout storage) "
@@ -168,8 +176,6 @@ def main():
     env, _ = task_registry.make_env("go2_locomotion", args=cli, env_cfg=cfg)
     runner, _ = task_registry.make_alg_runner(env, name="go2_locomotion", args=cli, train_cfg=tcfg, log_root=None)
 
-    sim = env.sim
-
     def barrier():
         torch.cuda.synchronize()
         if world > 1:
@@ -197,8 +203,54 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    if args.dump_outputs and rank == 0:                # before the kernel timings and rollouts below, which overwrite the storage
+    if args.dump_outputs and rank == 0:                # before --full's kernel timings and rollouts, which overwrite the storage
         dump_outputs(args.dump_outputs, timed_outputs(runner))
+    full = bbc_full(g, args, env, runner, dt, world, dev) if args.full else {}      # every rank: each times its own kernels
+    T = runner.num_steps_per_env
+    env_steps = args.num_envs * T * args.steps * world
+    value = env_steps / dt
+
+    if rank == 0:
+        out = {
+            "metric": "env-steps/sec (4096 Go2 envs) + wall-clock to 1k PPO iters, 1/2/4/8 GPU",
+            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": (f"go2_locomotion BBC + AMP (5 mocap gaits, {getattr(env, 'mocap_source', 'none')} clips: 17 labelled + 295 unlabelled), " if args.amp else
+                                    "go2_locomotion BBC, discriminator off, default-pose reset, ") +
+                                   f"{total_envs} envs in total = {args.num_envs} envs/GPU x {world}, {'plane' if args.terrain == 'plane' else 'height-field (trimesh course)'} terrain, 24 steps/iter, 5 epochs x 4 minibatches",
+                       "num_envs_total": total_envs, "num_envs_per_gpu": args.num_envs, "steps_per_iter": T, "parallelism": f"dp{world}"},
+            "wallclock_1k_iters_s": dt / args.steps * 1000.0,
+            **({"ranks": world, "collective": _collective_name(shared)} if world > 1 else {}),
+            **({"shared_gpu_harness": f"{world} ranks on ONE GPU, gloo collectives through host memory: bounds the data-parallel code path's own cost, says nothing about xGMI scaling",
+                "n_gpus": 1, "ranks": world} if shared else {}),
+            **full,
+        }
+        epochs, nmb = runner.alg.num_learning_epochs, runner.alg.num_mini_batches
+        samples = args.num_envs * T
+        if not args.amp:      # the discriminator's GEMMs are not counted, so the figure would overstate the AMP config
+            lf = samples * (epochs * UPDATE_FLOPS_PER_SAMPLE + ROLLOUT_FLOPS_PER_SAMPLE)
+            out["learner_roofline"] = {"bound": "mfma", "dtype": "f32", "achieved": lf / (dt / args.steps) / 1e12, "peak": FP32_MFMA_PEAK_TFLOPS,
+                                       "unit": "TFLOP/s", "frac": lf / (dt / args.steps) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
+                                       "algorithmic_flops_per_iteration": lf,
+                                       "note": f"whole iteration time; {epochs} epochs x {nmb} minibatches of {samples // nmb} samples, GEMMs through hipBLASLt (fp32 MFMA 16x16x4)"}
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(args.num_envs, args.cpu_seconds)
+    if world > 1 or forced_dp:
+        dist.destroy_process_group()
+    if rank == 0:
+        # RCCL's start-up banner sits in the C library's stdout buffer until somebody flushes it: do that first so the
+        # JSON line is the LAST line of output
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+        print(json.dumps(out), file=_RESULT_OUT, flush=True)
+
+
+def bbc_full(g, args, env, runner, dt, world, dev):
+    """--full, after the timed region of the behaviour-level bench: the rollout / update split and the env-step and policy kernels
+    timed live against their rooflines.  The keys it adds to the JSON line."""
+    import torch
+    sim, T = env.sim, runner.num_steps_per_env
     # live timing of the fused env-step kernel: HIP events around single launches on the launch stream, same process,
     # same env state, right after the timed region (inside it the 24 steps of a rollout replay as ONE hipGraph launch,
     # which leaves no place for per-kernel events; profiles/ holds the rocprofv3 per-kernel average of the same command)
@@ -241,8 +293,7 @@ def main():
         runner._collect(False, False)
         torch.cuda.synchronize(); roll.append(time.perf_counter() - t1)
         runner.alg.storage.clear()
-    coll = [sorted(roll)[len(roll) // 2]]
-    lrn = [dt / args.steps - coll[0]]
+    coll_s = sorted(roll)[len(roll) // 2]
     # live timing of the policy-inference kernel (qa_mlp_forward), same recipe as the env-step kernel
     chain, mlp_ms = runner._policy_chain(), None
     if chain is not None and chain.packed is not None:
@@ -257,62 +308,28 @@ def main():
             spans.append((e0, e1))
         torch.cuda.synchronize()
         mlp_ms = sorted(a.elapsed_time(b) for a, b in spans)[reps // 2] / per
-    T = runner.num_steps_per_env
-    env_steps = args.num_envs * T * args.steps * world
-    value = env_steps / dt
-
-    if rank == 0:
-        achieved = ALG_BYTES_PER_ENV_STEP * args.num_envs / (kern_ms * 1e-3) / 1e9
-        # the PMC pass on file is of the PLANE kernel with the lean export mask of a run without the discriminator (3); config 3 launches mask 1, the
-        # trimesh course the height-field kernel: neither is the kernel that was counted
-        if args.terrain != "plane" or args.amp:
-            traffic, traffic_note = None, "the PMC pass on file is of the plane kernel with lean exports 3 (config 2); this run launches another variant of the kernel"
-        else:
-            traffic, traffic_note = _stamped_traffic(g, args.num_envs)
-        out = {
-            "metric": "env-steps/sec (4096 Go2 envs) + wall-clock to 1k PPO iters, 1/2/4/8 GPU",
-            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": (f"go2_locomotion BBC + AMP (5 mocap gaits, {getattr(env, 'mocap_source', 'none')} clips: 17 labelled + 295 unlabelled), " if args.amp else
-                                    "go2_locomotion BBC, discriminator off, default-pose reset, ") +
-                                   f"{total_envs} envs in total = {args.num_envs} envs/GPU x {world}, {'plane' if args.terrain == 'plane' else 'height-field (trimesh course)'} terrain, 24 steps/iter, 5 epochs x 4 minibatches",
-                       "num_envs_total": total_envs, "num_envs_per_gpu": args.num_envs, "steps_per_iter": T, "parallelism": f"dp{world}"},
-            "wallclock_1k_iters_s": dt / args.steps * 1000.0,
-            **({"ranks": world, "collective": _collective_name(shared)} if world > 1 else {}),
-            **({"shared_gpu_harness": f"{world} ranks on ONE GPU, gloo collectives through host memory: bounds the data-parallel code path's own cost, says nothing about xGMI scaling",
-                "n_gpus": 1, "ranks": world} if shared else {}),
-            "rollout_env_steps_per_s": args.num_envs * T * world / (sum(coll) / len(coll)),
-            "collection_s": sum(coll) / len(coll), "learn_s": sum(lrn) / len(lrn),
-            "roofline": {"kernel": "qa_env_step_kernel", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note, "kernel_ms": kern_ms, "kernel_ms_back_to_back": kern_ms_alone, "rollout_graph": bool(getattr(runner, "_graph", None) is not None),
-                         "algorithmic_bytes_per_launch": ALG_BYTES_PER_ENV_STEP * args.num_envs,
-                         "note": "not byte-bound: 4096 envs = 256 workgroups = one per CU; the env's own wavefront is instruction-issue-bound (a Gauss-Seidel chain), r5 gives each workgroup two helper wavefronts on the CU's idle SIMDs for the substep's side chains, the non-foot rows, the history shift and the closing stores (69 -> 56 us back to back, DESIGN.md 4.1c, profiles/r5_env_step_helper_wavefronts.txt); traffic is the PMC figure of the lean-export kernel a training run launches (1.09x algorithmic); 16384 envs/GPU: 136 us per launch = 1.65x this rate (one-wavefront kernels: every SIMD has an env wavefront of its own there)"},
-        }
-        if mlp_ms is not None:
-            pf = ROLLOUT_FLOPS_PER_SAMPLE * args.num_envs
-            out["policy_roofline"] = {"kernel": "qa_mlp_forward_kernel", "bound": "mfma", "dtype": "f32", "achieved": pf / (mlp_ms * 1e-3) / 1e12,
-                                      "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": pf / (mlp_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
-                                      "kernel_ms": mlp_ms, "algorithmic_flops_per_launch": pf,
-                                      "note": "estimator + privileged encoder + actor + critic of one env step in one launch, activations in LDS (DESIGN.md 4.11)"}
-        epochs, nmb = runner.alg.num_learning_epochs, runner.alg.num_mini_batches
-        samples = args.num_envs * T
-        if not args.amp:      # the discriminator's GEMMs are not counted, so the figure would overstate the AMP config
-            lf = samples * (epochs * UPDATE_FLOPS_PER_SAMPLE + ROLLOUT_FLOPS_PER_SAMPLE)
-            out["learner_roofline"] = {"bound": "mfma", "dtype": "f32", "achieved": lf / (dt / args.steps) / 1e12, "peak": FP32_MFMA_PEAK_TFLOPS,
-                                       "unit": "TFLOP/s", "frac": lf / (dt / args.steps) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
-                                       "algorithmic_flops_per_iteration": lf,
-                                       "note": f"whole iteration time; {epochs} epochs x {nmb} minibatches of {samples // nmb} samples, GEMMs through hipBLASLt (fp32 MFMA 16x16x4)"}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.num_envs, args.cpu_seconds)
-    if world > 1 or forced_dp:
-        dist.destroy_process_group()
-    if rank == 0:
-        # RCCL's start-up banner sits in the C library's stdout buffer until somebody flushes it: do that first so the
-        # JSON line is the LAST line of output
-        import ctypes
-        ctypes.CDLL(None).fflush(None)
-        print(json.dumps(out), file=_RESULT_OUT, flush=True)
+    achieved = ALG_BYTES_PER_ENV_STEP * args.num_envs / (kern_ms * 1e-3) / 1e9
+    # the PMC pass on file is of the PLANE kernel with the lean export mask of a run without the discriminator (3); config 3 launches mask 1, the
+    # trimesh course the height-field kernel: neither is the kernel that was counted
+    if args.terrain != "plane" or args.amp:
+        traffic, traffic_note = None, "the PMC pass on file is of the plane kernel with lean exports 3 (config 2); this run launches another variant of the kernel"
+    else:
+        traffic, traffic_note = _stamped_traffic(g, args.num_envs)
+    out = {
+        "rollout_env_steps_per_s": args.num_envs * T * world / coll_s,
+        "collection_s": coll_s, "learn_s": dt / args.steps - coll_s,
+        "roofline": {"kernel": "qa_env_step_kernel", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note, "kernel_ms": kern_ms, "kernel_ms_back_to_back": kern_ms_alone, "rollout_graph": bool(getattr(runner, "_graph", None) is not None),
+                     "algorithmic_bytes_per_launch": ALG_BYTES_PER_ENV_STEP * args.num_envs,
+                     "note": "not byte-bound: 4096 envs = 256 workgroups = one per CU; the env's own wavefront is instruction-issue-bound (a Gauss-Seidel chain), r5 gives each workgroup two helper wavefronts on the CU's idle SIMDs for the substep's side chains, the non-foot rows, the history shift and the closing stores (69 -> 56 us back to back, DESIGN.md 4.1c, profiles/r5_env_step_helper_wavefronts.txt); traffic is the PMC figure of the lean-export kernel a training run launches (1.09x algorithmic); 16384 envs/GPU: 136 us per launch = 1.65x this rate (one-wavefront kernels: every SIMD has an env wavefront of its own there)"},
+    }
+    if mlp_ms is not None:
+        pf = ROLLOUT_FLOPS_PER_SAMPLE * args.num_envs
+        out["policy_roofline"] = {"kernel": "qa_mlp_forward_kernel", "bound": "mfma", "dtype": "f32", "achieved": pf / (mlp_ms * 1e-3) / 1e12,
+                                  "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": pf / (mlp_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
+                                  "kernel_ms": mlp_ms, "algorithmic_flops_per_launch": pf,
+                                  "note": "estimator + privileged encoder + actor + critic of one env step in one launch, activations in LDS (DESIGN.md 4.11)"}
+    return out
 
 
 ENV_KERNEL_SOURCES = ("qa_sim.hip", "qa_physics.h", "qa_device.h", "qa_go2_model.h")
@@ -476,8 +493,34 @@ def bench_tsc(args, world, rank, local_rank, dev):
         print("per-iteration ms:", " ".join(f"{v:.1f}" for v in iter_ms), file=sys.stderr)
     _barrier_sync(world)
     dt = _max_over_ranks(time.perf_counter() - t0, world, dev)
-    if args.dump_outputs and rank == 0:                # before the rollouts below, which overwrite the storage
+    if args.dump_outputs and rank == 0:                # before --full's rollouts, which overwrite the storage
         dump_outputs(args.dump_outputs, timed_outputs(runner, storage=not args.vision))
+    T = tcfg["depth_encoder"]["num_steps_per_env"] if args.vision else runner.num_steps_per_env
+    full = tsc_full(args, env, runner, n, T, dt, world, dev) if args.full else {}      # every rank: each times its own kernels
+    what = ("TSC-student with depth-camera obs (58x87 ray-cast depth image per env step, depth encoder + GRU + student actor, DAgger + BYOL)" if args.vision else
+            "TSC-teacher agility course")
+    out = {"metric": "env-steps/sec (4096 Go2 envs) + wall-clock to 1k PPO iters, 1/2/4/8 GPU", "value": n * T * args.steps * world / dt, "unit": "env-steps/s",
+           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+           "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": f"{what} (6 obstacles/env as height-field + ceiling collision terrain, randomize_base_mass/com, push_robots, randomize_start, "
+                                  f"action noise U(0.8,1.2), frozen behaviour policy + discriminator at their initial weights), {total} envs in total = {n} envs/GPU x {world}, "
+                                  f"{T} steps/iter" + ("" if args.vision else ", 5 epochs x 4 minibatches"),
+                      "num_envs_total": total, "num_envs_per_gpu": n, "steps_per_iter": T, "parallelism": f"dp{world}"},
+           **full}
+    if world > 1:
+        out["ranks"], out["collective"] = world, _collective_name(os.environ.get("QA_BENCH_SHARED_GPU") == "1")
+    if args.vision:
+        out["vision"] = dict(runner.last_vision)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline_tsc(min(n, 1024), args.cpu_seconds, bool(args.vision))
+    if rank == 0:
+        print(json.dumps(out), file=_RESULT_OUT, flush=True)
+
+
+def tsc_full(args, env, runner, n, T, dt, world, dev):
+    """--full, after the timed region of the task-level bench: the rollout / update split, the env-side kernels of one step and the
+    behaviour policy timed live against their rooflines.  The keys it adds to the JSON line."""
+    import torch
     # the two phases of an iteration, measured apart AFTER the timed region between device syncs (inside it the host never waits for the
     # GPU -- a recorded rollout returns to the host in ~1 ms -- so the runner's own host clocks are not phase times)
     coll_s = None
@@ -506,7 +549,6 @@ def bench_tsc(args, world, rank, local_rank, dev):
             fn()
         e1.record(); torch.cuda.synchronize()
         spans[name] = e0.elapsed_time(e1) / 40
-    T = tcfg["depth_encoder"]["num_steps_per_env"] if args.vision else runner.num_steps_per_env
     kern_ms = sum(spans.values())
     alg_bytes = TSC_ALG_BYTES_PER_ENV_STEP + (DEPTH_ALG_BYTES_PER_ENV_STEP if args.vision else 0)
     achieved = alg_bytes * n / (kern_ms * 1e-3) / 1e9
@@ -518,26 +560,13 @@ def bench_tsc(args, world, rank, local_rank, dev):
                                      _stamped_traffic(g, n, sized if os.path.exists(os.path.join(ROOT, "profiles", sized)) else "tsc_env_step_traffic.json"))
     if tsc_traffic is not None and tsc_traffic / (kern_ms * 1e-3) / 1e9 > HBM_PEAK_GBS:      # a figure that implies more than the HBM peak is not a measurement
         tsc_traffic, tsc_traffic_note = None, f"the figure on file ({tsc_traffic} B per env step) over {kern_ms * 1e3:.0f} us would be {tsc_traffic / (kern_ms * 1e-3) / 1e12:.1f} TB/s: void"
-    what = ("TSC-student with depth-camera obs (58x87 ray-cast depth image per env step, depth encoder + GRU + student actor, DAgger + BYOL)" if args.vision else
-            "TSC-teacher agility course")
-    out = {"metric": "env-steps/sec (4096 Go2 envs) + wall-clock to 1k PPO iters, 1/2/4/8 GPU", "value": n * T * args.steps * world / dt, "unit": "env-steps/s",
-           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-           "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": f"{what} (6 obstacles/env as height-field + ceiling collision terrain, randomize_base_mass/com, push_robots, randomize_start, "
-                                  f"action noise U(0.8,1.2), frozen behaviour policy + discriminator at their initial weights), {total} envs in total = {n} envs/GPU x {world}, "
-                                  f"{T} steps/iter" + ("" if args.vision else ", 5 epochs x 4 minibatches"),
-                      "num_envs_total": total, "num_envs_per_gpu": n, "steps_per_iter": T, "parallelism": f"dp{world}"},
-           "collection_s": coll_s, "learn_s": (dt / args.steps - coll_s) if coll_s is not None else None,
+    out = {"collection_s": coll_s, "learn_s": (dt / args.steps - coll_s) if coll_s is not None else None,
            "rollout_env_steps_per_s": (n * T * world / coll_s) if coll_s is not None else None,
            "phase_split": "rollout alone between device syncs after the timed region (median of 5); update = iteration - rollout" if coll_s is not None else "not split (learn_vision interleaves env steps and the student's forward passes)",
            "roofline": {"kernel": "qa_env_step_kernel<false,4,1> + qa_tsc_goal_step + qa_tsc_observations" + (" + qa_tsc_depth_kernel" if args.vision else ""),
                         "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": tsc_traffic, "traffic_source": tsc_traffic_note, "kernel_ms": kern_ms, "kernel_ms_each": spans,
                         "algorithmic_bytes_per_launch": alg_bytes * n}}
-    if world > 1:
-        out["ranks"], out["collective"] = world, _collective_name(os.environ.get("QA_BENCH_SHARED_GPU") == "1")
-    if args.vision:
-        out["vision"] = dict(runner.last_vision)
     chain = getattr(runner, "_bbc_chain", None)
     if chain is not None and chain.packed is not None:      # the frozen behaviour policy of the two-level loop: one qa_mlp_forward launch per env step
         obs_bbc = env.get_observations_bbc()
@@ -551,10 +580,7 @@ def bench_tsc(args, world, rank, local_rank, dev):
         out["policy_roofline"] = {"kernel": "qa_mlp_forward_kernel (behaviour policy, history-encoder variant, no critic)", "bound": "mfma", "dtype": "f32",
                                   "achieved": pf / (ms * 1e-3) / 1e12, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                                   "frac": pf / (ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, "kernel_ms": ms, "algorithmic_flops_per_launch": pf}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline_tsc(min(n, 1024), args.cpu_seconds, bool(args.vision))
-    if rank == 0:
-        print(json.dumps(out), file=_RESULT_OUT, flush=True)
+    return out
 
 
 def cpu_baseline_tsc(num_envs, budget_s, vision):
