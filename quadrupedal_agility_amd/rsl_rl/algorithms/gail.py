@@ -20,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.optim as optim
 
+from quadrupedal_agility_amd.rsl_rl import recording
 from quadrupedal_agility_amd.rsl_rl.algorithms import fused as fused_mod
 from quadrupedal_agility_amd.rsl_rl.algorithms.fused import ClipAdam, disc_loss, disc_prepare, ppo_loss
 from quadrupedal_agility_amd.rsl_rl.storage import ReplayBuffer, RolloutStorage
@@ -367,7 +368,6 @@ class SSInfoGAIL:
                 torch.cuda.synchronize()
                 for o in (self.optim_ac, self.optim_estimator):
                     o.zero_grad(set_to_none=True)
-                from quadrupedal_agility_amd.rsl_rl.runners.on_policy_runner import _no_gc
                 self._recording_ac = True
                 graphs = []
                 pool = torch.cuda.graph_pool_handle()
@@ -375,48 +375,33 @@ class SSInfoGAIL:
                     # r6: steps that run as chain launches are short (~0.37 ms), and two consecutive replays are ~8.5 us apart on the device: the
                     # nmb slots of an epoch as ONE recording (one replay per epoch)
                     epoch_graph = sync is None and self._train_chain_rows(mb) is not None and os.environ.get("QA_STEP_UNROLL", "1") != "0"
+
+                    def slot(i):
+                        stats, kl = front(i)
+                        self._ac_apply(kl)
+                        fused_mod.accumulate_scalars(self._acc_ac, stats)       # (one launch; was torch.stack + add_)
+
+                    def epoch():
+                        for i in range(nmb):
+                            slot(i)
+                            for o in (self.optim_ac, self.optim_estimator):
+                                o.zero_grad(set_to_none=True)
+
                     if epoch_graph:
-                        g = torch.cuda.CUDAGraph()
-                        with _no_gc(), torch.cuda.graph(g, pool=pool):
-                            for i in range(nmb):
-                                stats, kl = front(i)
-                                self._ac_apply(kl)
-                                fused_mod.accumulate_scalars(self._acc_ac, stats)       # (one launch; was torch.stack + add_)
-                                for o in (self.optim_ac, self.optim_estimator):
-                                    o.zero_grad(set_to_none=True)
-                        graphs.append((g, None, None))
+                        graphs.append((recording.record(epoch, pool=pool)[0], None, None))
                     for i in range(0 if epoch_graph else nmb):
                         if sync is None:
-                            g = torch.cuda.CUDAGraph()
-                            with _no_gc(), torch.cuda.graph(g, pool=pool):
-                                stats, kl = front(i)
-                                self._ac_apply(kl)
-                                fused_mod.accumulate_scalars(self._acc_ac, stats)
-                            graphs.append((g, None, None))
+                            graphs.append((recording.record(lambda: slot(i), pool=pool)[0], None, None))
                         else:
-                            ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                            with _no_gc(), torch.cuda.graph(ga, pool=pool):
-                                stats, kl = front(i)
-                                grads = [p.grad for p in all_params if p.grad is not None]
-                                packed = grads + [kl.detach().reshape(1)]
-                                bucket = torch._utils._flatten_dense_tensors(packed)       # lives in the graphs' pool
-                                stats_tmp = torch.stack(stats)
-                            with _no_gc(), torch.cuda.graph(gb, pool=pool):
-                                bucket.div_(sync.world)
-                                parts = torch._utils._unflatten_dense_tensors(bucket, packed)
-                                torch._foreach_copy_(grads, list(parts[:len(grads)]))
-                                self._ac_apply(parts[-1].reshape(()))
-                                self._acc_ac.add_(stats_tmp)
-                            graphs.append((ga, gb, bucket))
+                            graphs.append(recording.record_data_parallel(lambda: front(i)[::-1], self._ac_apply, self._acc_ac, all_params, sync.world, pool))
                         for o in (self.optim_ac, self.optim_estimator):       # the next slot's recording creates its gradients afresh
                             o.zero_grad(set_to_none=True)
                     self._ac_graph = graphs
                 finally:
                     self._recording_ac = False
-            except Exception as e:      # never fatal
-                print(f"[ppo update graph] capture failed, staying eager: {e}")
+            except Exception as e:
+                recording.capture_failed("ppo update graph", e)
                 self._ac_graph = False
-                torch.cuda.synchronize()
                 acc = torch.zeros(6, device=dev)
                 for sample in st.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
                     acc += torch.stack(self.update_actor_critic(sample))
@@ -429,12 +414,8 @@ class SSInfoGAIL:
             perm = torch.randperm(nmb * mb, device=dev)   # one permutation for all epochs (rollout_storage.py:122-157)
         fused_mod.gather_rows(perm, self._gather_srcs, dsts=self._perm_bufs)
         for _ in range(self.num_learning_epochs):
-            for i in range(len(self._ac_graph)):            # nmb recordings of one step each, or one of the whole epoch
-                ga, gb, bucket = self._ac_graph[i]
-                ga.replay()
-                if gb is not None:
-                    self.grad_sync.all_reduce_(bucket)
-                    gb.replay()
+            for ga, gb, bucket in self._ac_graph:            # nmb recordings of one step each, or one of the whole epoch
+                recording.replay_step(ga, gb, bucket, self.grad_sync)
         return self._acc_ac.clone()
 
     def _disc_updates_recorded(self, n_steps, mb, tables=None):
@@ -487,8 +468,6 @@ class SSInfoGAIL:
                 torch.cuda.synchronize()
                 for o in (self.optim_d, self.optim_q_eps, self.optim_q_c):
                     o.zero_grad(set_to_none=True)
-                g = torch.cuda.CUDAGraph()
-                from quadrupedal_agility_amd.rsl_rl.runners.on_policy_runner import _no_gc
                 # recorded on a stream of its own: the library GEMM workspace is keyed by the stream a launch is recorded on,
                 # and this step is replayed CONCURRENTLY with the PPO step's recording (update(), "overlap")
                 if self._disc_stream is None:
@@ -499,16 +478,17 @@ class SSInfoGAIL:
                     # r6: `unroll` steps per recording (a divisor of n_steps): two consecutive replays are ~8.5 us apart on the device, 0.7 ms of an
                     # 80-step chain whose steps are ~0.26 ms; the steps read their row block through the device-side counter, so a replay is k steps
                     unroll = max((k for k in (8, 5, 4, 2, 1) if n_steps % k == 0), default=1) if os.environ.get("QA_STEP_UNROLL", "1") != "0" else 1
-                    with _no_gc(), torch.cuda.graph(g, stream=self._disc_stream):
+
+                    def steps():
                         for _ in range(unroll):
                             one_step()
+                    g, _ = recording.record(steps, stream=self._disc_stream)
                 finally:
                     self._recording_disc = False
                 self._disc_graph, self._disc_unroll, self._disc_graph_steps = g, unroll, n_steps
-            except Exception as e:      # never fatal
-                print(f"[disc update graph] capture failed, staying eager: {e}")
+            except Exception as e:
+                recording.capture_failed("disc update graph", e)
                 self._disc_graph = False
-                torch.cuda.synchronize()
                 acc = torch.zeros(11, device=dev)
                 gens = zip(self.disc_storage.feed_forward_generator(n_steps, mb), self.motion_loader.feed_forward_generator_lb(n_steps, mb),
                            self.motion_loader.feed_forward_generator_ulb(n_steps, mb))
@@ -1065,15 +1045,10 @@ class SSInfoGAIL:
                         self._dg_acc.add_(self._dagger_step(flat_obs[self._dg_idx]))
                     torch.cuda.synchronize()
                     self.optim_hist_encoder.zero_grad(set_to_none=True)
-                    from quadrupedal_agility_amd.rsl_rl.runners.on_policy_runner import _no_gc
-                    g = torch.cuda.CUDAGraph()
-                    with _no_gc(), torch.cuda.graph(g):
-                        one_step()
-                    self._dagger_graph = g
+                    self._dagger_graph, _ = recording.record(one_step)
                 except Exception as e:
-                    print(f"[dagger update graph] capture failed, staying eager: {e}")
+                    recording.capture_failed("dagger update graph", e)
                     self._dagger_graph = False
-                    torch.cuda.synchronize()
             if self._dagger_graph:
                 self._dg_acc.zero_()
                 if perm is None:

@@ -8,8 +8,6 @@ torch.distributed initialised (one process per GPU, RCCL) every rank owns num_en
 gradient buckets / normalisation statistics are all-reduced.
 """
 import json
-import contextlib
-import gc
 import os
 import statistics
 import time
@@ -20,6 +18,7 @@ import torch
 import torch.distributed as dist
 
 from quadrupedal_agility_amd.legged_gym.utils.torch_jit_utils import compute_flat_key_pos
+from quadrupedal_agility_amd.rsl_rl import recording
 from quadrupedal_agility_amd.rsl_rl.algorithms import SSInfoGAIL  # noqa: F401  (resolved by name from the cfg)
 from quadrupedal_agility_amd.rsl_rl.algorithms.discriminator import Discriminator
 from quadrupedal_agility_amd.rsl_rl.datasets.motion_loader import MotionLoader
@@ -47,21 +46,6 @@ def _make_writer(log_dir):
         return SummaryWriter(log_dir=log_dir, flush_secs=10)
     except Exception:
         return _ScalarLog(log_dir)
-
-
-@contextlib.contextmanager
-def _no_gc():
-    """No cyclic garbage collection while a stream is capturing: a collection that happens to run inside the capture can
-    destroy old device objects (graphs, tensors with recorded events), whose destructors call HIP APIs that are illegal
-    during capture and abort the process.  (torch.cuda.graph collects once on entry; this keeps it from running again.)"""
-    was = gc.isenabled()
-    gc.collect()
-    gc.disable()
-    try:
-        yield
-    finally:
-        if was:
-            gc.enable()
 
 
 class GradSync:
@@ -410,20 +394,20 @@ class OnPolicyRunner:
                 with torch.inference_mode():
                     alg.act(self._obs_cur, self._obs_cur, hist_encoding)          # touch every GEMM shape once outside the capture
                 torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
                 alg.storage.step = 0
-                with _no_gc(), torch.cuda.graph(g):
+
+                def rollout():
                     with torch.inference_mode():
-                        ep_infos = self._rollout_steps(hist_encoding, logging, recorded=True)    # host side effects run now, GPU work on replay
+                        return self._rollout_steps(hist_encoding, logging, recorded=True)
+                g, ep_infos = recording.record(rollout)
                 self._graphs[key] = (g, env.delay, ep_infos)
                 if not key:
                     self._graph = g
                 g.replay()
-            except Exception as e:      # never fatal: fall back to eager launches
-                print(f"[rollout graph] capture failed, staying eager: {e}")
+            except Exception as e:
+                recording.capture_failed("rollout graph", e)
                 self._graph, self._graph_failed = None, True
                 self._graphs = {}
-                torch.cuda.synchronize()
                 return self._collect(hist_encoding, logging)
         else:
             with torch.inference_mode():

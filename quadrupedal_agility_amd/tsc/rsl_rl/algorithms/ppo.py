@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 import torch.optim as optim
 
+from quadrupedal_agility_amd.rsl_rl import recording
 from quadrupedal_agility_amd.rsl_rl.algorithms import fused
 from quadrupedal_agility_amd.rsl_rl.algorithms.fused import ClipAdam
 from ..storage import RolloutStorage
@@ -53,6 +54,7 @@ class PPO:
         self.use_update_graph = os.environ.get("QA_TSC_UPDATE_GRAPH", "1") != "0"
         self.use_fused_loss = os.environ.get("QA_TSC_FUSED_LOSS", "1") != "0"
         self._graph, self._warm_updates, self._lr_dev, self._recordable = None, 0, None, None
+        self._dagger_graph, self._dagger_warm = None, 0
         self.if_depth = depth_encoder is not None
         if self.if_depth:
             self.depth_encoder, self.depth_encoder_paras, self.depth_actor = depth_encoder, depth_encoder_paras, depth_actor
@@ -431,7 +433,6 @@ class PPO:
         once per update for the whole rollout.  Data-parallel runs record the step as TWO graphs around the gradient collective:
         [gather .. both backward passes, gradients + KL packed into a persistent bucket] -> all-reduce(bucket) -> [unpack, LR rule,
         both Adam steps].  Returns the summed losses, or None when capture is not possible (the caller stays eager)."""
-        from quadrupedal_agility_amd.rsl_rl.runners.on_policy_runner import _no_gc
         dev, st, ac = self.device, self.storage, self.actor_critic
         batch = st.num_envs * st.num_transitions_per_env
         mb = batch // self.num_mini_batches
@@ -462,7 +463,7 @@ class PPO:
                 # update (the reference draws one permutation for all epochs, :122-170) and minibatch i is rows [i mb, (i + 1) mb) of that copy; the slots of an
                 # epoch are ONE recording -- 5 replays per update instead of 20 x (index copy, replay, gather).  The behaviour-level learner's scheme since r3.
                 nmb = self.num_mini_batches
-                self._epoch_graph = False
+                self._epoch_graph, self._bucket = False, None
                 if sync is None and cflat is None and os.environ.get("QA_STEP_UNROLL", "1") != "0":
                     srcs_all = flat + [self._hist_latent_all]
                     bufs = fused.gather_rows(torch.arange(nmb * mb, device=dev), srcs_all)          # (also fills the buffers for the warm-up pass below)
@@ -508,46 +509,31 @@ class PPO:
                 ac.distribution_d = ac.distribution_c = None
                 gc.collect()
                 self.optimizer.zero_grad(set_to_none=True); self.estimator_optimizer.zero_grad(set_to_none=True)
-                if self._epoch_graph:
-                    g = torch.cuda.CUDAGraph()
-                    with _no_gc(), torch.cuda.graph(g):
-                        for i in range(nmb):
-                            kl, stats = front_slot(i)
-                            apply(kl.reshape(()))
-                            self._add_stats(self._acc, stats)
-                            self.optimizer.zero_grad(set_to_none=True); self.estimator_optimizer.zero_grad(set_to_none=True)
-                    self._graph = (g, None)
-                elif sync is None:
-                    g = torch.cuda.CUDAGraph()
-                    with _no_gc(), torch.cuda.graph(g):
-                        kl, stats = front()
-                        apply(kl.reshape(()))
-                        self._add_stats(self._acc, stats)
-                    self._graph = (g, None)
+
+                def step(fwd_bwd, *slot):
+                    kl, stats = fwd_bwd(*slot)
+                    apply(kl.reshape(()))
+                    self._add_stats(self._acc, stats)
+
+                def epoch():
+                    for i in range(nmb):
+                        step(front_slot, i)
+                        self.optimizer.zero_grad(set_to_none=True); self.estimator_optimizer.zero_grad(set_to_none=True)
+
+                def front_stacked():          # the statistics as ONE tensor, an attribute like the bucket: both are read by every replay of the second graph
+                    kl, st_ = front()
+                    self._stats_tmp = st_ if torch.is_tensor(st_) else torch.stack(list(st_))
+                    return kl, self._stats_tmp
+
+                if self._epoch_graph or sync is None:
+                    self._graph = (recording.record(epoch if self._epoch_graph else lambda: step(front))[0], None)
                 else:
-                    ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                    pool = torch.cuda.graph_pool_handle()
-                    with _no_gc(), torch.cuda.graph(ga, pool=pool):
-                        kl, st_ = front()
-                        self._stats_tmp = st_ if torch.is_tensor(st_) else torch.stack(list(st_))
-                        grads = [p.grad for p in params if p.grad is not None]
-                        packed = grads + [kl.detach().reshape(1)]
-                        self._bucket = torch._utils._flatten_dense_tensors(packed)          # lives in the graphs' pool
-                    with _no_gc(), torch.cuda.graph(gb, pool=pool):
-                        self._bucket.div_(sync.world)
-                        parts = torch._utils._unflatten_dense_tensors(self._bucket, packed)
-                        torch._foreach_copy_(grads, list(parts[:len(grads)]))
-                        apply(parts[-1].reshape(()))
-                        self._acc.add_(self._stats_tmp)
+                    ga, gb, self._bucket = recording.record_data_parallel(front_stacked, apply, self._acc, params, sync.world, torch.cuda.graph_pool_handle())
                     self._graph = (ga, gb)
                 # the capture ran no kernels: parameters, Adam moments and the LR are untouched; the replays below do this update
-            except Exception as e:      # never fatal: the eager loop is the same arithmetic
-                print(f"[tsc ppo update graph] capture failed, staying eager: {e}")
-                if os.environ.get("QA_DEBUG_GRAPH"):
-                    import traceback
-                    traceback.print_exc()
+            except Exception as e:
+                recording.capture_failed("tsc ppo update graph", e)
                 self._graph = False
-                torch.cuda.synchronize()
                 if self._lr_dev is not None:
                     lr = float(self._learning_rate)
                     self._lr_dev = None
@@ -568,10 +554,7 @@ class PPO:
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 self._mb_idx.copy_(perm[i * mb:(i + 1) * mb])
-                ga.replay()
-                if gb is not None:
-                    self.grad_sync.all_reduce_(self._bucket)
-                    gb.replay()
+                recording.replay_step(ga, gb, self._bucket, self.grad_sync)
         return self._acc.clone()
 
     def _dagger_step(self, obs):
@@ -602,32 +585,25 @@ class PPO:
         mb = (st.num_envs * st.num_transitions_per_env) // self.num_mini_batches
         obs_all = st.observations.flatten(0, 1)
         perm = torch.randperm(self.num_mini_batches * mb, requires_grad=False, device=self.device)      # one permutation for all epochs (:122-170)
-        graph = self.__dict__.setdefault("_dagger_graph", None)
-        warm = self.__dict__.setdefault("_dagger_warm", 0)
-        if (self.use_update_graph and graph is not False and warm >= 1 and fused.ENABLED and self.use_fused_loss and self.grad_sync is None
+        if (self.use_update_graph and self._dagger_graph is not False and self._dagger_warm >= 1 and fused.ENABLED and self.use_fused_loss and self.grad_sync is None
                 and torch.device(self.device).type == "cuda"):
-            if graph is None:
+            if self._dagger_graph is None:
                 try:
-                    from quadrupedal_agility_amd.rsl_rl.runners.on_policy_runner import _no_gc
                     self._dg_idx = torch.zeros(mb, dtype=torch.int64, device=self.device)
                     self._dg_acc = torch.zeros((), device=self.device)
                     self._dg_rows = (obs_all.data_ptr(), mb)
                     torch.cuda.synchronize()
                     self.hist_encoder_optimizer.zero_grad(set_to_none=True)
-                    g = torch.cuda.CUDAGraph()
-                    with _no_gc(), torch.cuda.graph(g):
-                        self._dg_acc.add_(self._dagger_step(obs_all[self._dg_idx]))
-                    graph = self._dagger_graph = g
-                except Exception as e:      # never fatal: the eager loop is the same arithmetic
-                    print(f"[tsc dagger update graph] capture failed, staying eager: {e}")
-                    graph = self._dagger_graph = False
-                    torch.cuda.synchronize()
-            if graph and self._dg_rows == (obs_all.data_ptr(), mb):
+                    self._dagger_graph, _ = recording.record(lambda: self._dg_acc.add_(self._dagger_step(obs_all[self._dg_idx])))
+                except Exception as e:
+                    recording.capture_failed("tsc dagger update graph", e)
+                    self._dagger_graph = False
+            if self._dagger_graph and self._dg_rows == (obs_all.data_ptr(), mb):
                 self._dg_acc.zero_()
                 for _ in range(self.num_learning_epochs):
                     for i in range(self.num_mini_batches):
                         self._dg_idx.copy_(perm[i * mb:(i + 1) * mb])
-                        graph.replay()
+                        self._dagger_graph.replay()
                 self._dagger_warm += 1
                 st.clear()
                 self.update_counter()
@@ -636,7 +612,7 @@ class PPO:
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 total += self._dagger_step(obs_all[perm[i * mb:(i + 1) * mb]])
-        self._dagger_warm = warm + 1
+        self._dagger_warm += 1
         st.clear()
         self.update_counter()
         return (total / n).item()

@@ -19,6 +19,7 @@ from copy import deepcopy
 import torch
 import torch.distributed as dist
 
+from quadrupedal_agility_amd.rsl_rl import recording
 from quadrupedal_agility_amd.rsl_rl.utils.utils import Normalizer, TorchNormalizer
 from quadrupedal_agility_amd.tsc.rsl_rl.algorithms import PPO, Discriminator
 from quadrupedal_agility_amd.tsc.rsl_rl.modules import ActorCriticBBC, ActorCriticTSC, Estimator
@@ -281,25 +282,20 @@ class OnPolicyRunner:
                 self._rollout_warm += 1
                 with torch.inference_mode():
                     return self._rollout_steps(hist_encoding, logging)
-            from quadrupedal_agility_amd.rsl_rl.runners.on_policy_runner import _no_gc
             try:
                 self._behaviour_policy()
                 torch.cuda.synchronize()
                 counters = (env.global_counter, env.total_env_steps_counter, env.common_step_counter)
-                g = torch.cuda.CUDAGraph()
                 alg.storage.step = 0
-                with _no_gc(), torch.cuda.graph(g):
+
+                def rollout():
                     with torch.inference_mode():
-                        ep_infos = self._rollout_steps(hist_encoding, logging)      # host side effects run now, GPU work on replay
+                        return self._rollout_steps(hist_encoding, logging)
+                self._rollout_graphs[key] = recording.record(rollout)
                 env.global_counter, env.total_env_steps_counter, env.common_step_counter = counters
-                self._rollout_graphs[key] = (g, ep_infos)
-            except Exception as e:      # never fatal: the eager loop is the same code
-                print(f"[tsc rollout graph] capture failed, staying eager: {e}")
-                if os.environ.get("QA_DEBUG_GRAPH"):
-                    import traceback
-                    traceback.print_exc()
+            except Exception as e:
+                recording.capture_failed("tsc rollout graph", e)
                 self._rollout_graphs[key] = False
-                torch.cuda.synchronize()
                 alg.storage.step = 0
                 with torch.inference_mode():
                     return self._rollout_steps(hist_encoding, logging)
@@ -382,21 +378,13 @@ class OnPolicyRunner:
                 vs["warm"].add(upd)
                 recordable = False
             else:
-                from quadrupedal_agility_amd.rsl_rl.runners.on_policy_runner import _no_gc
                 counters = (env.global_counter, env.total_env_steps_counter, env.common_step_counter)
                 try:
                     torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with _no_gc(), torch.cuda.graph(g):
-                        out = body()                      # host side effects run now, GPU work on replay
-                    graphs[upd] = (g, out)
-                except Exception as e:                    # never fatal: the eager step is the same code
-                    print(f"[tsc vision env-step graph] capture failed, staying eager: {e}")
-                    if os.environ.get("QA_DEBUG_GRAPH"):
-                        import traceback
-                        traceback.print_exc()
+                    graphs[upd] = recording.record(body)
+                except Exception as e:
+                    recording.capture_failed("tsc vision env-step graph", e)
                     graphs[upd] = False
-                    torch.cuda.synchronize()
                     recordable = False
                 env.global_counter, env.total_env_steps_counter, env.common_step_counter = counters
         if recordable:

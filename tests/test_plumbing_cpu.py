@@ -127,3 +127,136 @@ def test_buffers_that_recorded_launches_read_keep_their_addresses():
     nz.update_torch([torch.randn(50, 4) * 3 + 1, torch.randn(20, 4)])
     assert (nz.mean.data_ptr(), nz.var.data_ptr(), nz.count.data_ptr()) == ptrs
     assert float(nz.count) == __import__("pytest").approx(70.0001, abs=1e-3) and float(nz.mean.abs().max()) > 0.1
+
+
+# ------------------------------------------------------------------ rsl_rl/recording.py: the ceremony of recording a hipGraph, with the device faked
+class _FakeCapture:
+    """torch.cuda.CUDAGraph / torch.cuda.graph / torch.cuda.synchronize stand-ins: a `with` body runs at once on the CPU and `log` keeps what happened"""
+
+    def __init__(self, monkeypatch):
+        import contextlib
+        import gc
+        self.log = log = []
+
+        class Graph:
+            def replay(self):
+                log.append(("replay", self))
+
+        @contextlib.contextmanager
+        def graph(g, pool=None, stream=None):
+            log.append(("capture", g, pool, stream, gc.isenabled()))
+            yield
+            log.append(("end", g))
+
+        monkeypatch.setattr(torch.cuda, "CUDAGraph", Graph)
+        monkeypatch.setattr(torch.cuda, "graph", graph)
+        monkeypatch.setattr(torch.cuda, "synchronize", lambda: log.append(("synchronize",)))
+
+
+def test_no_gc_restores_the_collector():
+    import gc
+    from quadrupedal_agility_amd.rsl_rl import recording
+    assert gc.isenabled()
+    collections = []
+    real = gc.collect
+    try:
+        gc.collect = lambda *a: collections.append(gc.isenabled()) or real(*a)
+        with pytest.raises(KeyError):
+            with recording.no_gc():
+                assert not gc.isenabled()
+                raise KeyError("body")
+        assert gc.isenabled()                   # restored although the body raised
+        assert collections == [True]            # one collection on entry, before the collector is switched off
+        gc.disable()
+        with recording.no_gc():
+            assert not gc.isenabled()
+        assert not gc.isenabled()               # was off on entry: stays off
+    finally:
+        gc.collect = real
+        gc.enable()
+
+
+def test_record_runs_the_body_under_capture_and_returns_graph_and_result(monkeypatch):
+    from quadrupedal_agility_amd.rsl_rl import recording
+    fake = _FakeCapture(monkeypatch)
+    g, out = recording.record(lambda: fake.log.append(("body",)) or 42, pool="POOL", stream="STREAM")
+    assert isinstance(g, torch.cuda.CUDAGraph) and out == 42
+    assert fake.log == [("capture", g, "POOL", "STREAM", False), ("body",), ("end", g)]      # collector off inside, nothing synchronised or zeroed for the caller
+    fake.log.clear()
+    g2, _ = recording.record(lambda: None)
+    assert fake.log[0] == ("capture", g2, None, None, False) and g2 is not g
+    with pytest.raises(ZeroDivisionError):      # a failing body is the site's to catch
+        recording.record(lambda: 1 / 0)
+    import gc
+    assert gc.isenabled()
+
+
+def test_capture_failed_prints_the_tagged_line_and_the_traceback_only_when_asked(monkeypatch, capsys):
+    from quadrupedal_agility_amd.rsl_rl import recording
+    fake = _FakeCapture(monkeypatch)
+
+    def fail(tag):
+        try:
+            recording.record(lambda: {}["missing tensor"])
+        except Exception as e:
+            recording.capture_failed(tag, e)
+
+    monkeypatch.delenv("QA_DEBUG_GRAPH", raising=False)
+    fail("ppo update graph")
+    out, err = capsys.readouterr()
+    assert out == "[ppo update graph] capture failed, staying eager: 'missing tensor'\n"
+    assert "Traceback" not in out + err
+    assert fake.log[-1] == ("synchronize",) and fake.log.count(("synchronize",)) == 1
+    monkeypatch.setenv("QA_DEBUG_GRAPH", "1")
+    fail("tsc rollout graph")
+    out, err = capsys.readouterr()
+    assert out.startswith("[tsc rollout graph] capture failed, staying eager: 'missing tensor'\n")
+    assert "Traceback (most recent call last)" in out + err and "KeyError: 'missing tensor'" in out + err and "in record" in out + err
+    assert fake.log[-1] == ("synchronize",) and fake.log.count(("synchronize",)) == 2
+
+
+def test_data_parallel_pair_packs_reduces_and_applies_in_order(monkeypatch):
+    from quadrupedal_agility_amd.rsl_rl import recording
+    fake = _FakeCapture(monkeypatch)
+    log = fake.log
+    for mod, name in ((torch._utils, "_flatten_dense_tensors"), (torch._utils, "_unflatten_dense_tensors"), (torch, "_foreach_copy_")):
+        def wrapped(*a, _f=getattr(mod, name), _n=name):
+            log.append((_n, a[0].clone() if torch.is_tensor(a[0]) else [t.clone() for t in a[0]]))
+            return _f(*a)
+        monkeypatch.setattr(mod, name, wrapped)
+    params = [torch.nn.Parameter(torch.zeros(2, 3)), torch.nn.Parameter(torch.zeros(4)), torch.nn.Parameter(torch.zeros(5))]      # the last one gets no gradient
+    g0, g1 = torch.arange(6.0).view(2, 3) + 1, torch.arange(4.0) - 8
+    acc = torch.tensor([10.0, 20.0])
+
+    def front():
+        log.append(("front",))
+        params[0].grad, params[1].grad = g0.clone(), g1.clone()
+        return torch.tensor([[0.5]]), (torch.tensor(3.0), torch.tensor(4.0))
+
+    def apply(kl):
+        log.append(("apply", kl.clone(), params[0].grad.clone(), params[1].grad.clone(), acc.clone()))
+
+    ga, gb, bucket = recording.record_data_parallel(front, apply, acc, params, 2, "POOL")
+    names = [e[0] for e in log]
+    assert names == ["capture", "front", "_flatten_dense_tensors", "end", "capture", "_unflatten_dense_tensors", "_foreach_copy_", "apply", "end"]
+    assert log[0][1:4] == (ga, "POOL", None) and log[4][1:4] == (gb, "POOL", None) and ga is not gb
+    flat = torch.cat([g0.view(-1), g1, torch.tensor([0.5])])
+    assert bucket.shape == (11,) and torch.equal(bucket, flat / 2) and float(bucket[-1]) * 2 == 0.5       # [gradients | KL], the mean over the 2 ranks
+    assert torch.equal(log[5][1], flat / 2)                                 # divided BEFORE it is unpacked
+    assert torch.equal(log[6][1][0], g0) and torch.equal(log[6][1][1], g1)      # the copy's destinations are the parameters' own gradients ...
+    _, kl, grad0, grad1, acc_then = log[7]
+    assert kl.shape == () and float(kl) == 0.25
+    assert torch.equal(grad0, g0 / 2) and torch.equal(grad1, g1 / 2)        # ... and they hold the mean when the optimiser runs
+    assert torch.equal(acc_then, torch.tensor([10.0, 20.0])) and torch.equal(acc, torch.tensor([13.0, 24.0]))       # statistics (stacked) go on last
+    assert params[0].grad.data_ptr() != bucket.data_ptr()
+
+    class Sync:
+        def all_reduce_(self, t):
+            log.append(("all_reduce", t))
+
+    log.clear()
+    recording.replay_step(ga, gb, bucket, Sync())
+    assert log == [("replay", ga), ("all_reduce", bucket), ("replay", gb)] and log[1][1] is bucket
+    log.clear()
+    recording.replay_step(ga, None, None, None)          # a step recorded as one graph
+    assert log == [("replay", ga)]
