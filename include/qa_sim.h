@@ -447,7 +447,10 @@ int qa_narrow_wgrad(const float *grad_out, const float *x, int64_t rows, int32_t
  * (tsc/rsl_rl/algorithms/ppo.py:160-282) run them, what PyTorch issues as addmm + elu (forward) and elu_backward + mm + mm^T + sum(0)
  * (backward).  All matrices fp32 row-major with explicit leading dimensions (so a column slice of a wider row -- e.g. the
  * proprioceptive block of the 671-wide observation -- is an operand without a copy); weight = nn.Linear.weight (out, in).
- * act: 0 none, 1 ELU(alpha), 2 ReLU.  fp32 in, fp32 accumulate: the reference's dtype.
+ * act: 0 none, 1 ELU(alpha), 2 ReLU, and -- the three linear entry points below only, the window GEMMs of the convolutions take 0..2 -- the FORWARD
+ * codes of the policy chain's table for the reference's other activations: 3 tanh, 7 LeakyReLU(0.01), 8 SELU, 9 sigmoid (QA_MLP_ACT_*; 4..6 are
+ * not activations here).  `act_prev` names the activation whose derivative is taken, from its output: tanh 1 - y^2, LeakyReLU y > 0 ? 1 : 0.01,
+ * SELU y > 0 ? lambda : y + lambda alpha, sigmoid y (1 - y); `alpha` is read by ELU only.  fp32 in, fp32 accumulate: the reference's dtype.
  *   qa_linear_forward          y[r][o]  = act( sum_k x[r][k] weight[o][k] + bias[o] )                    (bias may be NULL)
  *   qa_linear_backward_input   gin[r][k] = ( sum_o gout[r][o] weight[o][k] ) * act'(y_prev[r][k])        act' from the activation OUTPUT
  *                              y_prev of the layer that produced x (ELU: y > 0 ? 1 : y + alpha; ReLU: y > 0; act_prev 0: no factor,
@@ -825,7 +828,26 @@ int qa_disc_prepare(const float *const *batches, const int64_t *rows, int32_t nu
  *   QA_MLP_LOAD          dst[:, dst_col : +n] = outs[aux_index][:, aux_col : aux_col+n]: a second (third, ...) input of the chain read from global memory
  *                        into a scratch buffer (the gradients at several heads arrive as separate tensors); QA_MLP_F_SAVE writes the loaded columns
  *                        out again at (out_index, out_col), e.g. to assemble them into one matrix for a weight-gradient product.
- * Ops written before ABI 17 (new fields zero) mean what they meant. */
+ * Ops written before ABI 17 (new fields zero) mean what they meant.
+ * The reference's other activations (policy.activation, bbc/rsl_rl/modules/actor_critic.py:228-245) are further act codes -- data, no new entry
+ * point, ABI 18 as before; the codes 0..6 keep their numbers and their arithmetic:
+ *   act 7 / 8 / 9        forward: LeakyReLU(0.01) (x > 0 ? x : 0.01 x), SELU (lambda (x > 0 ? x : alpha (e^x - 1)), lambda = 1.0507009873554805,
+ *                        alpha = 1.6732632423543772), sigmoid (1 / (1 + e^-x))
+ *   act 10 / 11 / 12     their derivatives from the saved output y, used exactly as 4..6 are: y > 0 ? 1 : 0.01;  y > 0 ? lambda : y + lambda alpha;
+ *                        y (1 - y).  A derivative code is its forward code + 3 (as 4..6 are for 1..3). */
+#define QA_MLP_ACT_NONE 0
+#define QA_MLP_ACT_ELU 1
+#define QA_MLP_ACT_RELU 2
+#define QA_MLP_ACT_TANH 3
+#define QA_MLP_ACT_ELU_GRAD 4
+#define QA_MLP_ACT_RELU_GRAD 5
+#define QA_MLP_ACT_TANH_GRAD 6
+#define QA_MLP_ACT_LRELU 7
+#define QA_MLP_ACT_SELU 8
+#define QA_MLP_ACT_SIGMOID 9
+#define QA_MLP_ACT_LRELU_GRAD 10
+#define QA_MLP_ACT_SELU_GRAD 11
+#define QA_MLP_ACT_SIGMOID_GRAD 12
 #define QA_MLP_COPY 0
 #define QA_MLP_LAYER 1
 #define QA_MLP_GRAD 2
@@ -849,7 +871,7 @@ typedef struct qa_mlp_op {
     int32_t flags;                         /* QA_MLP_F_* (ABI 17; `reserved`, zero, before) */
     int64_t w_off, b_off;
     int32_t out_col;                       /* ABI 17: first column of outs[out_index] the op writes */
-    int32_t aux_index, aux_col;            /* ABI 17: act 4..6: the saved activation */
+    int32_t aux_index, aux_col;            /* ABI 17: act 4..6 and 10..12: the saved activation */
     int32_t pad_;
 } qa_mlp_op;
 int64_t qa_mlp_packed_floats(const qa_mlp_op *ops, int32_t num_ops);

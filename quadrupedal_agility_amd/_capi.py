@@ -273,6 +273,9 @@ class QaAdamStackTensor(C.Structure):
 MLP_COPY, MLP_LAYER, MLP_GRAD, MLP_LOAD, MLP_MAX_OPS, MLP_MAX_OUTPUTS = 0, 1, 2, 3, 24, 8
 MLP_F_SAVE, MLP_F_TRANSPOSED, MLP_F_ADD = 1, 2, 4
 MLP_ACT_ELU_GRAD, MLP_ACT_RELU_GRAD, MLP_ACT_TANH_GRAD = 4, 5, 6
+# the reference's other activations (QA_MLP_ACT_* of include/qa_sim.h; data of ABI 18, no new entry point): forward codes, and the derivative codes = forward + 3
+MLP_ACT_NONE, MLP_ACT_ELU, MLP_ACT_RELU, MLP_ACT_TANH, MLP_ACT_LRELU, MLP_ACT_SELU, MLP_ACT_SIGMOID = 0, 1, 2, 3, 7, 8, 9
+MLP_ACT_LRELU_GRAD, MLP_ACT_SELU_GRAD, MLP_ACT_SIGMOID_GRAD = 10, 11, 12
 MLP_BUF_COLS = (800, 576, 320, 128)
 
 TSC_REWARD_NAMES = ("action_hl_rate", "collision", "feet_edge", "latent_c_rate", "reach_goal", "tracking_goal_vel", "tracking_yaw",

@@ -218,6 +218,27 @@ static __device__ __forceinline__ void gemm_frag(float (&f)[4], const float *__r
     }
 }
 
+// The reference's other activations (include/qa_sim.h: the forward codes of the policy chain's table; 1 and 2 keep the expressions they had in the
+// epilogues).  g.act is a kernel argument, so the switch is a scalar branch.
+static constexpr float SELU_LAMBDA = 1.0507009873554805f, SELU_ALPHA = 1.6732632423543772f;
+static __host__ __device__ constexpr bool gemm_act_ok(int act) { return (act >= 0 && act <= QA_MLP_ACT_TANH) || (act >= QA_MLP_ACT_LRELU && act <= QA_MLP_ACT_SIGMOID); }
+static __device__ __forceinline__ float gemm_act_hi(int act, float v) {
+    switch (act) {
+        case QA_MLP_ACT_TANH: return tanhf(v);
+        case QA_MLP_ACT_LRELU: return v > 0.f ? v : 0.01f * v;
+        case QA_MLP_ACT_SELU: return SELU_LAMBDA * (v > 0.f ? v : SELU_ALPHA * (expf(v) - 1.f));
+        default: return 1.f / (1.f + expf(-v));          // QA_MLP_ACT_SIGMOID
+    }
+}
+static __device__ __forceinline__ float gemm_dact_hi(int act, float y) {
+    switch (act) {
+        case QA_MLP_ACT_TANH: return 1.f - y * y;
+        case QA_MLP_ACT_LRELU: return y > 0.f ? 1.f : 0.01f;
+        case QA_MLP_ACT_SELU: return y > 0.f ? SELU_LAMBDA : y + SELU_LAMBDA * SELU_ALPHA;
+        default: return y * (1.f - y);
+    }
+}
+
 // the epilogue of both kernels: the lane holds out[b][a .. a+3] for each of its TA x TB tiles (MFMA D rows = 4 consecutive a)
 template <int BA, int BB, int EPI, bool ONES>
 static __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, const f4 (&acc)[BA / 32][BB / 32], const f4 (&oacc)[BB / 32], int a_base, int b_base,
@@ -252,6 +273,9 @@ static __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, const f4
                 } else if (g.act == 2) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+                } else if (g.act > 2) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = gemm_act_hi(g.act, v[r]);
                 }
             }
             if (EPI == 2 && g.yprev && g.act != 0) {
@@ -264,8 +288,13 @@ static __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, const f4
                     if (a + 2 < g.a_count) y.z = yp[2];
                     if (a + 3 < g.a_count) y.w = yp[3];
                 }
+                if (g.act <= 2) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] *= (g.act == 1) ? (y[r] > 0.f ? 1.f : y[r] + g.alpha) : (y[r] > 0.f ? 1.f : 0.f);
+                    for (int r = 0; r < 4; ++r) v[r] *= (g.act == 1) ? (y[r] > 0.f ? 1.f : y[r] + g.alpha) : (y[r] > 0.f ? 1.f : 0.f);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] *= gemm_dact_hi(g.act, y[r]);
+                }
             }
             float *o = out + (int64_t)b * g.ldo + a;
             if (full) *(f4 *)o = v;
@@ -576,6 +605,9 @@ static __device__ __forceinline__ void dma_epilogue(const GemmArgs &g, const f4 
                 } else if (g.act == 2) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+                } else if (g.act > 2) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = gemm_act_hi(g.act, v[r]);
                 }
             }
             if (EPI == 2 && g.yprev && g.act != 0) {
@@ -588,8 +620,13 @@ static __device__ __forceinline__ void dma_epilogue(const GemmArgs &g, const f4 
                     if (a + 2 < g.a_count) y.z = yp[2];
                     if (a + 3 < g.a_count) y.w = yp[3];
                 }
+                if (g.act <= 2) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] *= (g.act == 1) ? (y[r] > 0.f ? 1.f : y[r] + g.alpha) : (y[r] > 0.f ? 1.f : 0.f);
+                    for (int r = 0; r < 4; ++r) v[r] *= (g.act == 1) ? (y[r] > 0.f ? 1.f : y[r] + g.alpha) : (y[r] > 0.f ? 1.f : 0.f);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] *= gemm_dact_hi(g.act, y[r]);
+                }
             }
             float *o = out + (int64_t)b * g.ldo + a;
             if (full) *(f4 *)o = v;
@@ -755,7 +792,7 @@ __global__ void __launch_bounds__(256) qa_slab_bias_act_kernel(const float *__re
     for (; z < nsplit; ++z) s += *(const f4 *)(src + (int64_t)z * stride);
     if (bias) s += *(const f4 *)(bias + o);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) s[k] = act == 1 ? (s[k] > 0.f ? s[k] : alpha * (expf(s[k]) - 1.f)) : (act == 2 ? fmaxf(s[k], 0.f) : s[k]);
+    for (int k = 0; k < 4; ++k) s[k] = act == 1 ? (s[k] > 0.f ? s[k] : alpha * (expf(s[k]) - 1.f)) : (act == 2 ? fmaxf(s[k], 0.f) : act > 2 ? gemm_act_hi(act, s[k]) : s[k]);
     *(f4 *)(y + r * ldy + o) = s;
 }
 
@@ -875,7 +912,7 @@ void qa_gemm_force_config(int32_t cfg) { g_force_cfg = cfg; }
 int qa_linear_forward(const float *x, int64_t ldx, const float *weight, int64_t ldw, const float *bias, float *y, int64_t ldy, int64_t rows,
                       int32_t in_features, int32_t out_features, int32_t act, float alpha, void *stream) {
     if (!x || !weight || !y || rows <= 0 || rows > INT32_MAX || in_features <= 0 || out_features <= 0 || ldx < in_features || ldw < in_features ||
-        ldy < out_features || act < 0 || act > 2) { snprintf(g_gerr, sizeof(g_gerr), "qa_linear_forward: bad argument"); return QA_E_ARG; }
+        ldy < out_features || !gemm_act_ok(act)) { snprintf(g_gerr, sizeof(g_gerr), "qa_linear_forward: bad argument"); return QA_E_ARG; }
     if (!fits_u32(rows, ldx) || !fits_u32(out_features, ldw)) { snprintf(g_gerr, sizeof(g_gerr), "qa_linear_forward: rows * ldx (or out_features * ldw) >= 2^32 elements"); return QA_E_ARG; }
     GemmArgs g = {};
     g.A = weight; g.lda = ldw; g.a_count = out_features;
@@ -896,7 +933,7 @@ int qa_linear_backward_input(const float *grad_out, int64_t ldg, const float *we
                              float *grad_in, int64_t ldgi, int64_t rows, int32_t in_features, int32_t out_features, int32_t act_prev, float alpha,
                              void *stream) {
     if (!grad_out || !weight || !grad_in || rows <= 0 || rows > INT32_MAX || in_features <= 0 || out_features <= 0 || ldg < out_features ||
-        ldw < in_features || ldgi < in_features || act_prev < 0 || act_prev > 2 || (act_prev != 0 && (!y_prev || ldyp < in_features))) {
+        ldw < in_features || ldgi < in_features || !gemm_act_ok(act_prev) || (act_prev != 0 && (!y_prev || ldyp < in_features))) {
         snprintf(g_gerr, sizeof(g_gerr), "qa_linear_backward_input: bad argument"); return QA_E_ARG; }
     if (!fits_u32(rows, ldg) || !fits_u32(out_features, ldw)) { snprintf(g_gerr, sizeof(g_gerr), "qa_linear_backward_input: rows * ldg (or out_features * ldw) >= 2^32 elements"); return QA_E_ARG; }
     GemmArgs g = {};
@@ -1212,7 +1249,7 @@ int64_t qa_linear_forward_split_scratch_bytes(int64_t rows, int32_t in_features,
 int qa_linear_forward_split(const float *x, int64_t ldx, const float *weight, int64_t ldw, const float *bias, float *y, int64_t ldy, int64_t rows,
                             int32_t in_features, int32_t out_features, int32_t act, float alpha, void *scratch, int64_t scratch_bytes, void *stream) {
     if (!x || !weight || !y || !scratch || rows <= 0 || rows > INT32_MAX || in_features <= 0 || out_features <= 0 || out_features % 4 || ldx < in_features ||
-        ldw < in_features || ldy < out_features || ldy % 4 || act < 0 || act > 2 || !aligned16(y) || (bias && !aligned16(bias)) ||
+        ldw < in_features || ldy < out_features || ldy % 4 || !gemm_act_ok(act) || !aligned16(y) || (bias && !aligned16(bias)) ||
         !fits_u32(rows, ldx) || !fits_u32(out_features, ldw)) {
         snprintf(g_gerr, sizeof(g_gerr), "qa_linear_forward_split: bad argument (out features and ldy multiples of 4, y / bias 16-byte aligned)"); return QA_E_ARG; }
     if (scratch_bytes < qa_linear_forward_split_scratch_bytes(rows, in_features, out_features) || !aligned16(scratch)) {

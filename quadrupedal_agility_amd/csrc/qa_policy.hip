@@ -97,14 +97,31 @@ __device__ __forceinline__ float mlp_act(int act, float v, float y) {
     return act == 0 ? v : act == 1 ? elu1(v) : act == 2 ? fmaxf(v, 0.f) : act == 3 ? tanhf(v) :
            act == 4 ? v * (y > 0.f ? 1.f : y + 1.f) : act == 5 ? (y > 0.f ? v : 0.f) : v * (1.f - y * y);
 }
+/* ABI 18 data, no new entry point: the reference's other activations (actor_critic.py:228-245) above the codes 0..6.  Forward 7 LeakyReLU(0.01), 8 SELU,
+ * 9 sigmoid; derivative from the saved output 10 / 11 / 12 (= forward code + 3, as 4..6 are for 1..3).  expf, not __expf: these are not ELU's hot
+ * path, and sigmoid / SELU outputs are compared with torch's at the project's forward bound. */
+constexpr float SELU_LAMBDA = 1.0507009873554805f, SELU_ALPHA = 1.6732632423543772f;
+__host__ __device__ constexpr bool mlp_is_grad(int act) { return (act >= QA_MLP_ACT_ELU_GRAD && act <= QA_MLP_ACT_TANH_GRAD) || (act >= QA_MLP_ACT_LRELU_GRAD && act <= QA_MLP_ACT_SIGMOID_GRAD); }
+__host__ __device__ constexpr bool mlp_is_forward(int act) { return (act >= 0 && act <= 3) || (act >= QA_MLP_ACT_LRELU && act <= QA_MLP_ACT_SIGMOID); }
+__device__ __forceinline__ float mlp_act_hi(int act, float v, float y) {
+    switch (act) {
+        case QA_MLP_ACT_LRELU: return v > 0.f ? v : 0.01f * v;
+        case QA_MLP_ACT_SELU: return SELU_LAMBDA * (v > 0.f ? v : SELU_ALPHA * (expf(v) - 1.f));
+        case QA_MLP_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
+        case QA_MLP_ACT_LRELU_GRAD: return y > 0.f ? v : 0.01f * v;
+        case QA_MLP_ACT_SELU_GRAD: return v * (y > 0.f ? SELU_LAMBDA : y + SELU_LAMBDA * SELU_ALPHA);
+        default: return v * (y * (1.f - y));         /* QA_MLP_ACT_SIGMOID_GRAD */
+    }
+}
 
 /* one layer for this wavefront: TPW column tiles starting at tile t0.
  * The weight fragments are fetched PF-1 k-blocks ahead of their use into a ring of PF register stages (the L2 round trip is
  * several hundred cycles; one k-block of MFMAs is 128 * TPW cycles).  The sched_barriers keep the compiler from sinking the
  * prefetch back down to its use, which it otherwise does to shorten live ranges. */
 struct MlpPlace { int src_base, src_stride, dst_base, dst_stride; };      /* where the op's source / destination buffers are in LDS (floats) */
-/* EXT: the ABI 17 features (saved copies, derivative epilogues); the rollout's launches compile without them */
-template <int TPW, int PF = mlp_pf(TPW), bool EXT = false>
+/* EXT: the ABI 17 features (saved copies, derivative epilogues); the rollout's launches compile without them.  HI: the act codes above 6 (the opt-in
+ * two-group launch compiles without them and is not taken for a chain that has one: its eight column tiles per wave leave no register for them) */
+template <int TPW, int PF = mlp_pf(TPW), bool EXT = false, bool HI = true>
 __device__ __forceinline__ void mlp_layer(const MlpDevOp &op, const float *packed, float *lds, const MlpArgs &a, int row0, int wave, int lane, const MlpPlace pl) {
     const int nt = op.nt, kb = op.kb;
     const int t0 = wave * TPW;
@@ -126,7 +143,7 @@ __device__ __forceinline__ void mlp_layer(const MlpDevOp &op, const float *packe
     const int act = op.act;
     const int live = a.rows - (row0 + 4 * kq);              /* rows of this lane's group of 4 that exist */
     float yv[TPW][4];
-    if (EXT && act >= 4) {         /* the saved forward activation whose derivative scales the product (rows beyond the batch: the last row's, unused) */
+    if (EXT && mlp_is_grad(act)) {         /* the saved forward activation whose derivative scales the product (rows beyond the batch: the last row's, unused) */
         const int64_t as = a.out_stride[op.aux_index];
         const float *y = a.out[op.aux_index] + op.aux_col + m;
 #pragma unroll
@@ -186,15 +203,32 @@ __device__ __forceinline__ void mlp_layer(const MlpDevOp &op, const float *packe
     float *g = to_global ? a.out[op.out_index] + (int64_t)(row0 + 4 * kq) * os + op.out_col + m : nullptr;
     const int ds = pl.dst_stride;
     float *d = op.dst_buf >= 0 ? lds + pl.dst_base + (4 * kq) * ds + op.dst_col + m : nullptr;
+    if (!HI || act <= 6) {         /* op.act is wave-uniform: one scalar branch per layer, and the codes 0..6 keep the instruction stream they had */
 #pragma unroll
-    for (int i = 0; i < TPW; ++i) {
-        const int col = (t0 + i) * 16;
-        if (t0 + i < nt && col + m < op.n) {
+        for (int i = 0; i < TPW; ++i) {
+            const int col = (t0 + i) * 16;
+            if (t0 + i < nt && col + m < op.n) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float v = mlp_act(EXT ? act : (act > 3 ? 0 : act), acc[i][r] + bias[i], yv[i][r]);
-                if (d) d[r * ds + col] = v;
-                if (g && r < live) g[r * os + col] = v;
+                for (int r = 0; r < 4; ++r) {
+                    const float v = mlp_act(EXT ? act : (act > 3 ? 0 : act), acc[i][r] + bias[i], yv[i][r]);
+                    if (d) d[r * ds + col] = v;
+                    if (g && r < live) g[r * os + col] = v;
+                }
+            }
+        }
+    } else {
+        /* the launches without the ABI 17 features evaluate forward codes only (a derivative code there means "none", as for 4..6) */
+        const int hi = __builtin_amdgcn_readfirstlane((EXT || !mlp_is_grad(act)) ? act : 0);
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) {
+            const int col = (t0 + i) * 16;
+            if (t0 + i < nt && col + m < op.n) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = hi == 0 ? acc[i][r] + bias[i] : mlp_act_hi(hi, acc[i][r] + bias[i], yv[i][r]);
+                    if (d) d[r * ds + col] = v;
+                    if (g && r < live) g[r * os + col] = v;
+                }
             }
         }
     }
@@ -212,7 +246,10 @@ __device__ __forceinline__ void mlp_elementwise(const MlpDevOp &op, float *lds, 
                                          : lds[pl.src_base + r * pl.src_stride + op.src_col + c];
         float *d = lds + pl.dst_base + r * pl.dst_stride + op.dst_col + c;
         if (add) v += *d;
-        if (act >= 4) v = mlp_act(act, v, live ? a.out[op.aux_index][(int64_t)(row0 + r) * a.out_stride[op.aux_index] + op.aux_col + c] : 0.f);
+        if (mlp_is_grad(act)) {
+            const float y = live ? a.out[op.aux_index][(int64_t)(row0 + r) * a.out_stride[op.aux_index] + op.aux_col + c] : 0.f;
+            v = act <= 6 ? mlp_act(act, v, y) : mlp_act_hi(act, v, y);
+        }
         *d = v;
         if (save && live) a.out[op.out_index][(int64_t)(row0 + r) * a.out_stride[op.out_index] + op.out_col + c] = v;
     }
@@ -318,10 +355,10 @@ __global__ __launch_bounds__(MLP_WAVES * 64) void qa_mlp_forward_groups_kernel(M
             mlp_elementwise(op, lds, a, row0, gtid, GRP_WAVES * 64, pl);
         } else {
             const int per = (op.nt + GRP_WAVES - 1) / GRP_WAVES;      /* column tiles per wave of the group */
-            if (per <= 1) mlp_layer<1, 8>(op, a.packed, lds, a, row0, gw, lane, pl);
-            else if (per <= 2) mlp_layer<2, 8>(op, a.packed, lds, a, row0, gw, lane, pl);
-            else if (per <= 4) mlp_layer<4, 4>(op, a.packed, lds, a, row0, gw, lane, pl);
-            else mlp_layer<8, 4>(op, a.packed, lds, a, row0, gw, lane, pl);
+            if (per <= 1) mlp_layer<1, 8, false, false>(op, a.packed, lds, a, row0, gw, lane, pl);
+            else if (per <= 2) mlp_layer<2, 8, false, false>(op, a.packed, lds, a, row0, gw, lane, pl);
+            else if (per <= 4) mlp_layer<4, 4, false, false>(op, a.packed, lds, a, row0, gw, lane, pl);
+            else mlp_layer<8, 4, false, false>(op, a.packed, lds, a, row0, gw, lane, pl);
         }
         group_barrier(&s_arrive[grp], target, lane);
     }
@@ -459,8 +496,8 @@ static int mlp_check(const qa_mlp_op *ops, int32_t num_ops, const char *who) {
         bool ok = (layer || o.kind == QA_MLP_COPY || o.kind == QA_MLP_GRAD || o.kind == QA_MLP_LOAD) && o.src_buf >= 0 && o.src_buf < MLP_NBUF && o.src_col >= 0 && o.n > 0 &&
                   (o.flags & ~(QA_MLP_F_SAVE | QA_MLP_F_TRANSPOSED | QA_MLP_F_ADD)) == 0 && o.out_col >= 0;
         if (ok && (o.flags & QA_MLP_F_SAVE)) ok = o.out_index >= 0 && o.out_index < QA_MLP_MAX_OUTPUTS;
-        if (ok && ((layer && o.act >= 4) || (o.kind == QA_MLP_GRAD && o.act != 0)))
-            ok = o.act >= 4 && o.act <= 6 && o.aux_index >= 0 && o.aux_index < QA_MLP_MAX_OUTPUTS && o.aux_col >= 0;
+        if (ok && ((layer && mlp_is_grad(o.act)) || (o.kind == QA_MLP_GRAD && o.act != 0)))
+            ok = mlp_is_grad(o.act) && o.aux_index >= 0 && o.aux_index < QA_MLP_MAX_OUTPUTS && o.aux_col >= 0;
         if (ok && o.kind == QA_MLP_LOAD) {        /* global -> scratch buffer: no LDS source, no activation */
             ok = o.aux_index >= 0 && o.aux_index < QA_MLP_MAX_OUTPUTS && o.aux_col >= 0 && o.act == 0 && o.dst_buf > 0 && o.dst_buf < MLP_NBUF && o.dst_col >= 0 &&
                  o.dst_col + o.n <= buf_cols(o.dst_buf);
@@ -470,7 +507,7 @@ static int mlp_check(const qa_mlp_op *ops, int32_t num_ops, const char *who) {
         if (ok && layer) {
             const int kpad = mlp_kb(o.k, o.n) * 16;         /* columns the layer reads (beyond k: against zero weights) */
             /* reading past the row's padding lands in the next row / buffer (finite activations, zero weights): allowed while inside LDS */
-            ok = o.k > 0 && o.act >= 0 && o.act <= 6 && (o.src_col % 4) == 0 && o.src_col + o.k <= buf_cols(o.src_buf) + 4 &&
+            ok = o.k > 0 && (mlp_is_forward(o.act) || mlp_is_grad(o.act)) && (o.src_col % 4) == 0 && o.src_col + o.k <= buf_cols(o.src_buf) + 4 &&
                  lds_base(o.src_buf) + (MLP_ROWS - 1) * (buf_cols(o.src_buf) + 4) + o.src_col + kpad <= MLP_LDS_FLOATS && o.w_off >= 0 && o.b_off >= 0 && (o.w_off % 4) == 0 &&
                  (o.n + 15) / 16 <= 4 * MLP_WAVES;
             if (ok && o.dst_buf >= 0) ok = o.dst_buf > 0 && o.dst_buf < MLP_NBUF && o.dst_buf != o.src_buf && o.dst_col >= 0 && o.dst_col + o.n <= buf_cols(o.dst_buf);
@@ -563,7 +600,7 @@ int qa_mlp_forward(const float *x, int64_t x_stride, int32_t rows, int32_t x_col
             if (o.out_index >= num_outs || !outs[o.out_index] || out_strides[o.out_index] < o.out_col + o.n) {
                 snprintf(g_perr, sizeof(g_perr), "qa_mlp_forward: op %d writes output %d which is missing or too narrow", i, o.out_index); return QA_E_ARG; }
         }
-        if (((o.kind == QA_MLP_LAYER || o.kind == QA_MLP_GRAD) && o.act >= 4) || o.kind == QA_MLP_LOAD) {
+        if (((o.kind == QA_MLP_LAYER || o.kind == QA_MLP_GRAD) && mlp_is_grad(o.act)) || o.kind == QA_MLP_LOAD) {
             if (o.aux_index >= num_outs || !outs[o.aux_index] || out_strides[o.aux_index] < o.aux_col + o.n) {
                 snprintf(g_perr, sizeof(g_perr), "qa_mlp_forward: op %d reads the saved activation %d which is missing or too narrow", i, o.aux_index); return QA_E_ARG; }
         }
@@ -577,8 +614,10 @@ int qa_mlp_forward(const float *x, int64_t x_stride, int32_t rows, int32_t x_col
     /* a tile per CU or more: nothing to split over CUs -- two strands side by side inside every workgroup instead (qa_mlp_forward_groups_kernel),
      * when the chain has two and their buffers fit the CU's LDS; QA_MLP_GROUPS=1 in the environment / qa_mlp_set_groups(1) keeps the one-group kernel (A/B runs) */
     bool ext = false;           /* any ABI 17 feature in the program: the kernel variant that has them (the two-group launch does not) */
-    for (int i = 0; i < num_ops; ++i) ext |= ops[i].flags != 0 || ops[i].kind == QA_MLP_GRAD || ops[i].kind == QA_MLP_LOAD || ops[i].act >= 4 || ops[i].out_col != 0;
-    if (!ext && max_strands < 2 && mlp_groups_switch() >= 2 && mlp_strands(ops, num_ops, 2, strand_of) == 2 && mlp_group_geometry(ops, num_ops, strand_of, x_cols, a)) {
+    bool hi = false;            /* an act code above 6: the one-group kernels only */
+    for (int i = 0; i < num_ops; ++i) hi |= ops[i].act > 6;
+    for (int i = 0; i < num_ops; ++i) ext |= ops[i].flags != 0 || ops[i].kind == QA_MLP_GRAD || ops[i].kind == QA_MLP_LOAD || mlp_is_grad(ops[i].act) || ops[i].out_col != 0;
+    if (!ext && !hi && max_strands < 2 && mlp_groups_switch() >= 2 && mlp_strands(ops, num_ops, 2, strand_of) == 2 && mlp_group_geometry(ops, num_ops, strand_of, x_cols, a)) {
         static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(qa_mlp_forward_groups_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                             MLP_LDS_LIMIT_FLOATS * 4);
         if (attr == hipSuccess) {

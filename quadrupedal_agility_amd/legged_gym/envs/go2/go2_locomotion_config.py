@@ -226,6 +226,7 @@ class Go2LocomotionCfgAlgo(LeggedRobotCfgAlgo):
         train_with_estimated_explicit = True
         learning_rate = 1.0e-4
         hidden_dims = [128, 64]
+        activation = "elu"           # the reference's estimator is ELU whatever policy.activation says; set both alike for the chain launches / recorded steps
 
     class runner(LeggedRobotCfgAlgo.runner):
         experiment_idx = 0

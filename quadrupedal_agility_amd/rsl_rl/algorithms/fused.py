@@ -425,9 +425,78 @@ def linear_elu(x, weight, bias, alpha=1.0):
     return _LinearElu.apply(x, weight, bias, alpha)
 
 
+def linear_act(x, weight, bias, code, alpha=1.0):
+    """act(x W^T + b) for any activation of the table (`activation_code`): ELU as `linear_elu`, the others as a one-layer _MlpChain -- bias + activation
+    in the GEMM's epilogue, bias gradient out of qa_linear_backward_weight (the history encoder's layers, whatever policy.activation is)"""
+    if code == ACT_ELU:
+        return _LinearElu.apply(x, weight, bias, alpha)
+    return _MlpChain.apply(x, ((code, alpha),), weight, bias)
+
+
 OWN_FWD_NARROW = os.environ.get("QA_OWN_FWD_NARROW", "0") == "1"      # measured neutral end to end (31.2 vs 31.0 ms): off by default
 OWN_GEMM = os.environ.get("QA_OWN_GEMM", "1") != "0"      # the dense layers through csrc/qa_gemm.hip (0: library GEMMs + the r1/r2 kernels around them)
 ACT_NONE, ACT_ELU, ACT_RELU = 0, 1, 2
+# The reference's other activations (policy.activation: bbc/rsl_rl/modules/actor_critic.py:228-245).  ONE table of forward codes for the GEMM epilogues
+# (qa_linear_forward / _split / qa_linear_backward_input: `act_prev` names the activation whose derivative is taken) and for the chain launches
+# (qa_mlp_forward, whose derivative code is the forward code + 3): include/qa_sim.h QA_MLP_ACT_*.
+ACT_TANH, ACT_LRELU, ACT_SELU, ACT_SIGMOID = _capi.MLP_ACT_TANH, _capi.MLP_ACT_LRELU, _capi.MLP_ACT_SELU, _capi.MLP_ACT_SIGMOID
+NEW_ACTS = (ACT_TANH, ACT_LRELU, ACT_SELU, ACT_SIGMOID)
+SELU_LAMBDA, SELU_ALPHA = 1.0507009873554805, 1.6732632423543772
+
+
+def activation_code(m):
+    """(forward code, alpha) of an activation module of the reference's table -- ELU(alpha), ReLU, Tanh, LeakyReLU(0.01), SELU, Sigmoid -- else None"""
+    nn = torch.nn
+    if isinstance(m, nn.ELU):
+        return ACT_ELU, float(m.alpha)
+    if isinstance(m, nn.LeakyReLU):
+        return (ACT_LRELU, 0.0) if m.negative_slope == 0.01 else None
+    for cls, code in ((nn.ReLU, ACT_RELU), (nn.Tanh, ACT_TANH), (nn.SELU, ACT_SELU), (nn.Sigmoid, ACT_SIGMOID)):
+        if type(m) is cls:
+            return code, 0.0
+    return None
+
+
+def grad_code(code):
+    """the chain launches' derivative-from-the-saved-output code of a forward code (0 stays 0)"""
+    return code + 3 if code else 0
+
+
+def activation_derivative(code, y, alpha=1.0):
+    """act'(x) from the activation's OUTPUT y, elementwise torch ops (the table of DESIGN 4.22; the kernels' epilogues evaluate the same expressions)"""
+    if code == ACT_ELU:
+        return torch.where(y > 0, torch.ones_like(y), y + alpha)
+    if code == ACT_RELU:
+        return (y > 0).to(y.dtype)
+    if code == ACT_TANH:
+        return 1.0 - y * y
+    if code == ACT_LRELU:
+        return torch.where(y > 0, torch.ones_like(y), torch.full_like(y, 0.01))
+    if code == ACT_SELU:
+        return torch.where(y > 0, torch.full_like(y, SELU_LAMBDA), y + SELU_LAMBDA * SELU_ALPHA)
+    if code == ACT_SIGMOID:
+        return y * (1.0 - y)
+    raise ValueError(f"no activation with code {code}")
+
+
+def uniform_kinds(codes):
+    """The uniformity rule of the fast paths: the activation codes of a policy's layers are acceptable when they are the kinds the kernels always
+    took side by side (ELU, ReLU) or ONE of the other kinds throughout -- what `get_activation` produces.  A mixed stack is declined."""
+    kinds = {c for c in codes if c != ACT_NONE}
+    return kinds <= {ACT_ELU, ACT_RELU} or len(kinds) == 1
+
+
+def uniform_activation(*nets):
+    """the forward code every activation module of `nets` shares, or None (no activation module at all, an unknown one, or a mixed stack)"""
+    codes = set()
+    for net in nets:
+        for m in (net.modules() if net is not None else ()):
+            if isinstance(m, ELEMENTWISE_ACTIVATIONS) and not isinstance(m, (torch.nn.Identity, torch.nn.Flatten)):
+                ca = activation_code(m)
+                if ca is None:
+                    return None
+                codes.add(ca[0])
+    return codes.pop() if len(codes) == 1 else None
 
 
 def _check(rc, name):
@@ -580,7 +649,9 @@ class _MlpChain(torch.autograd.Function):
         w0p = saved[-1] if kpad else None
         g = _rows2d(gy)
         act_top, alpha_top = spec[-1]
-        if act_top != ACT_NONE:        # the chain ends in an activation (encoders): its derivative has no GEMM above it to ride on
+        if act_top in NEW_ACTS:        # ... of the other kinds: one elementwise product (no reduction: the bias gradient comes from qa_linear_backward_weight)
+            g = g * activation_derivative(act_top, acts[L])
+        elif act_top != ACT_NONE:      # the chain ends in an activation (encoders): its derivative has no GEMM above it to ride on
             g, _ = _masked_colsum(g, acts[L]) if act_top == ACT_RELU else _elu_bwd(g, acts[L], alpha_top)
         grads = [None] * (2 * L)
         gx = None
@@ -613,20 +684,24 @@ def _elu_bwd(gy, y, alpha):
 
 
 def _chain_spec(mods):
-    """[(Linear, act code, alpha), ...] when `mods` is a plain stack of Linear layers each optionally followed by ELU / ReLU, else None"""
+    """[(Linear, act code, alpha), ...] when `mods` is a plain stack of Linear layers each optionally followed by an activation of the reference's
+    table (`activation_code`), ELU and ReLU side by side or one of the other kinds throughout (`uniform_kinds`), else None"""
     out, i = [], 0
     while i < len(mods):
         m = mods[i]
         if not (isinstance(m, torch.nn.Linear) and m.bias is not None):
             return None
         nxt = mods[i + 1] if i + 1 < len(mods) else None
+        ca = activation_code(nxt) if nxt is not None and not isinstance(nxt, torch.nn.Linear) else None
         if isinstance(nxt, torch.nn.ELU):
             out.append((m, ACT_ELU, float(nxt.alpha))); i += 2
         elif isinstance(nxt, torch.nn.ReLU):
             out.append((m, ACT_RELU, 0.0)); i += 2
+        elif ca is not None:
+            out.append((m, ca[0], ca[1])); i += 2
         else:
             out.append((m, ACT_NONE, 0.0)); i += 1
-    return out or None
+    return out if out and uniform_kinds(a for _, a, _ in out) else None
 
 
 def _flatten(mods):
@@ -639,8 +714,9 @@ def _flatten(mods):
 def mlp_chain(mods, x):
     """Run a stack of modules (Sequentials are flattened, so a trunk and its head are ONE stack) on a 2-D ROCm tensor under autograd.
     Consecutive narrow layers (`own_layer`) form one _MlpChain of hand-written GEMMs; the wide trunk layers go through `linear_elu` /
-    `linear_relu` (library GEMM + our ELU-backward / bias / slab-sum kernels).  Anything the stack does not cover (other activations, CPU
-    tensors, no_grad) takes the modules as they are."""
+    `linear_relu` (library GEMM + our ELU-backward / bias / slab-sum kernels).  A stack with one of the other activations of the reference's table
+    (tanh, LeakyReLU, SELU, sigmoid) is ONE _MlpChain whatever `own_layer` says: the library route needs the ELU- / ReLU-specific backward kernels
+    behind it.  Anything the stack does not cover (unknown activations, CPU tensors, no_grad) takes the modules as they are."""
     flat = _flatten(mods)
     spec = _chain_spec(flat) if (ENABLED and OWN_GEMM and x.is_cuda and torch.is_grad_enabled() and x.dim() == 2 and x.dtype == torch.float32) else None
     if spec is None:
@@ -652,12 +728,13 @@ def mlp_chain(mods, x):
             else:
                 x = m(x)
         return x
+    every = any(a in NEW_ACTS for _, a, _ in spec)
     i = 0
     while i < len(spec):
         m, act, alpha = spec[i]
-        if own_layer(m.in_features, m.out_features):
+        if every or own_layer(m.in_features, m.out_features):
             j = i
-            while j < len(spec) and own_layer(spec[j][0].in_features, spec[j][0].out_features):
+            while j < len(spec) and (every or own_layer(spec[j][0].in_features, spec[j][0].out_features)):
                 j += 1
             params = []
             for mm, _, _ in spec[i:j]:
@@ -707,7 +784,7 @@ def recordable(*nets):
     OUR kernels: torch's batch reductions (the bias gradient of F.linear / conv: `sum(0)`) go stale or unwritten under hipGraph replay on
     this ROCm (profiles/r2_hipgraph_stale_reductions.md).  Whitelist: nn.Linear WITH a bias inside nn.Sequential stacks run through
     `mlp_forward` / `mlp_chain` (any width, any elementwise activation after it), the history encoder's Conv1d layers (evaluated as
-    window-gather + `linear_elu` when their activation is ELU), bare parameters (`std`).  Anything else -> stay eager."""
+    window-gather + `linear_act` when their activation is one of the reference's table), bare parameters (`std`).  Anything else -> stay eager."""
     if not (ENABLED and OWN_GEMM):
         return False
     from quadrupedal_agility_amd.rsl_rl.modules.actor_critic import StateHistoryEncoder
@@ -726,7 +803,7 @@ def recordable(*nets):
             elif own and not all(p.dim() <= 1 for p in own):
                 return False
         for mod in net.modules():
-            if isinstance(mod, StateHistoryEncoder) and not isinstance(mod.activation_fn, torch.nn.ELU) and any(p.requires_grad for p in mod.parameters()):
+            if isinstance(mod, StateHistoryEncoder) and activation_code(mod.activation_fn) is None and any(p.requires_grad for p in mod.parameters()):
                 return False
             if isinstance(mod, torch.nn.Conv1d) and not any(isinstance(h, StateHistoryEncoder) and mod in list(h.modules()) for h in net.modules()):
                 if any(p.requires_grad for p in mod.parameters()):
@@ -1462,8 +1539,9 @@ class PolicyChain:
         return ((k + 15) // 16 + pf - 1) // pf * pf
 
     @staticmethod
-    def _linears(seq):
-        """[(Linear, elu?)] of an nn.Sequential of Linear / ELU(alpha=1) modules, None for anything else"""
+    def _linears(seq, table=False):
+        """[(Linear, act code)] of an nn.Sequential of Linear / ELU(alpha=1) / ReLU modules, None for anything else.  `table`: every activation of
+        the reference's table (`activation_code`; the behaviour-level policy's descriptions, which then hold the codes to `uniform_kinds`)"""
         import torch.nn as nn
         mods = list(seq) if isinstance(seq, nn.Sequential) else [seq]
         out = []
@@ -1474,6 +1552,8 @@ class PolicyChain:
                 out[-1][1] = 1
             elif isinstance(m, nn.ReLU) and out and out[-1][1] == 0:
                 out[-1][1] = 2
+            elif table and not isinstance(m, nn.ELU) and activation_code(m) is not None and out and out[-1][1] == 0:
+                out[-1][1] = activation_code(m)[0]
             else:
                 return None
         return out
@@ -1511,7 +1591,8 @@ class PolicyChain:
 
     @classmethod
     def describe(cls, actor_critic, estimator, use_estimator, hist_encoding=False, with_critic=True, estimate_col=None):
-        """-> PolicyChain, or None when the modules are not plain Linear/ELU stacks that fit the kernel's buffers.
+        """-> PolicyChain, or None when the modules are not plain Linear + activation stacks that fit the kernel's buffers (activations: the reference's
+        table, ELU(alpha=1) and ReLU side by side or one other kind throughout -- `uniform_kinds`).
         hist_encoding=True describes the variant whose latent comes from the history encoder (rollouts of every
         dagger_update_freq-th iteration, play.py, the exported policy): its per-frame Linear and its two Conv1d layers are
         each ONE layer op over the t-major window buffer, with the structured matrix (block-diagonal / banded) built from the
@@ -1524,16 +1605,22 @@ class PolicyChain:
         n_obs = ac.num_critic_obs
         n_cmd = n_obs - cmd0
         n_in = n_prop + n_exp + n_lat + n_cmd
-        stacks = dict(actor=cls._linears(ac.actor_trunk))
+        stacks = dict(actor=cls._linears(ac.actor_trunk, True))
         if with_critic:
-            stacks["critic"] = cls._linears(ac.critic_trunk)
+            stacks["critic"] = cls._linears(ac.critic_trunk, True)
         use_priv = ac.train_with_estimated_latent and not hist_encoding and not isinstance(ac.priv_encoder, nn.Identity)
         use_hist = ac.train_with_estimated_latent and hist_encoding
         if use_priv:
-            stacks["priv"] = cls._linears(ac.priv_encoder)
+            stacks["priv"] = cls._linears(ac.priv_encoder, True)
         if use_estimator:
-            stacks["est"] = cls._linears(estimator.estimator)
-        if any(v is None for v in stacks.values()) or n_obs > cls.BUF_COLS[0] or n_in > cls.BUF_COLS[3] or cmd0 + n_cmd != n_obs:
+            stacks["est"] = cls._linears(estimator.estimator, True)
+        he_act = 0
+        if use_hist:
+            ca = activation_code(ac.history_encoder.activation_fn)
+            he_act = ca[0] if ca is not None and (ca[0] != ACT_ELU or ca[1] == 1.0) else None
+        if he_act is None or any(v is None for v in stacks.values()) or not uniform_kinds([a for v in stacks.values() for _, a in v] + [he_act]):
+            return None       # an activation outside the table, or a mixed stack
+        if n_obs > cls.BUF_COLS[0] or n_in > cls.BUF_COLS[3] or cmd0 + n_cmd != n_obs:
             return None
         stacks["actor"] = stacks["actor"] + [[ac.actor_head, 0]]
         if with_critic:
@@ -1589,8 +1676,7 @@ class PolicyChain:
         if use_hist:        # first: it borrows buffer 3 (the actor-input buffer Z) for the first convolution's output
             he = ac.history_encoder
             convs = [m for m in he.conv_layers if isinstance(m, nn.Conv1d)]
-            elu = isinstance(he.activation_fn, nn.ELU) and he.activation_fn.alpha == 1.0
-            if len(convs) != 2 or not elu or any(c.padding[0] or c.dilation[0] != 1 or c.bias is None for c in convs):
+            if len(convs) != 2 or any(c.padding[0] or c.dilation[0] != 1 or c.bias is None for c in convs):
                 return None
             enc, outl, T = he.encoder[0], he.linear_output[0], he.tsteps
             (c1, c2) = convs
@@ -1618,10 +1704,10 @@ class PolicyChain:
             copy(0, hist0, 1, 0, T * n_prop)
             if est_in_obs:
                 ok &= chain(stacks["est"], 0, 0, n_prop, ("buf", 1, estimate_col - hist0), {1}) and stacks["est"][-1][0].out_features == n_exp
-            ok &= layer(1, 0, T * n_prop, 2, 0, T * C0, 1, 0, lambda: torch.block_diag(*([enc.weight] * T)).contiguous(), rep(enc.bias, T))
-            ok &= layer(2, 0, T * C0, 3, 0, T1 * C1, 1, 0, conv_matrix(c1, T, T1), rep(c1.bias, T1))
-            ok &= layer(3, 0, T1 * C1, 1, 0, T2 * C2, 1, 0, conv_matrix(c2, T1, T2), rep(c2.bias, T2))
-            ok &= layer(1, 0, T2 * C2, Z, lat_col, n_lat, 1, 0,
+            ok &= layer(1, 0, T * n_prop, 2, 0, T * C0, he_act, 0, lambda: torch.block_diag(*([enc.weight] * T)).contiguous(), rep(enc.bias, T))
+            ok &= layer(2, 0, T * C0, 3, 0, T1 * C1, he_act, 0, conv_matrix(c1, T, T1), rep(c1.bias, T1))
+            ok &= layer(3, 0, T1 * C1, 1, 0, T2 * C2, he_act, 0, conv_matrix(c2, T1, T2), rep(c2.bias, T2))
+            ok &= layer(1, 0, T2 * C2, Z, lat_col, n_lat, he_act, 0,
                         lambda: outl.weight.view(n_lat, C2, T2).permute(0, 2, 1).reshape(n_lat, T2 * C2).contiguous(), outl.bias)
         copy(0, 0, Z, 0, n_prop)
         if use_estimator and not est_in_obs:

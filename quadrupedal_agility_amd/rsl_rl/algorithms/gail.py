@@ -309,6 +309,9 @@ class SSInfoGAIL:
     def _recordable_networks(self):
         other = (nn.SELU, nn.ReLU, nn.LeakyReLU, nn.Tanh, nn.Sigmoid, nn.GELU, nn.SiLU)
         plain = not any(isinstance(m, other) for net in (self.actor_critic, self.estimator) for m in net.modules())
+        # ... or ONE activation of the reference's table throughout (policy.activation): its layers run on the hand-written GEMMs / chain launches,
+        # whose bias gradients are our own column sums.  A mixed stack stays eager.
+        plain = plain or (fused_mod.OWN_GEMM and fused_mod.uniform_activation(self.actor_critic, self.estimator) is not None)
         disc_ok = (not self.amp_enabled) or (self.disc._relu_trunk() is not None and self.disc_loss_function == "MSELoss")
         return bool(fused_mod.ENABLED and plain and disc_ok)
 

@@ -177,12 +177,14 @@ class PpoTrainChain:
     @classmethod
     def describe(cls, ac, estimator, rows, lib=None, prefix="qa_"):
         import torch.nn as nn
-        lin = fused.PolicyChain._linears
+        lin = lambda seq: fused.PolicyChain._linears(seq, True)
         st = dict(actor=lin(ac.actor_trunk), critic=lin(ac.critic_trunk), est=lin(estimator.estimator),
                   priv=None if isinstance(ac.priv_encoder, nn.Identity) else lin(ac.priv_encoder))
         if not ENABLED or rows > MAX_ROWS or any(v is None for v in st.values()) or not ac.train_with_estimated_latent or ac.fixed_std:
             return None
-        if (any(a != 1 for k in ("actor", "critic", "priv") for _, a in st[k]) or any(a != 1 for _, a in st["est"][:-1]) or st["est"][-1][1] != 0
+        # ONE activation throughout (what get_activation produces): ELU(alpha = 1) or one of the other kinds of the reference's table -- a mixed stack is declined
+        E = st["actor"][0][1]
+        if (E == 0 or any(a != E for k in ("actor", "critic", "priv") for _, a in st[k]) or any(a != E for _, a in st["est"][:-1]) or st["est"][-1][1] != 0
                 or len(st["actor"]) != 3 or len(st["critic"]) != 3 or len(st["priv"]) != 2 or len(st["est"]) != 3):
             return None
         sl = ac._sl
@@ -213,7 +215,7 @@ class PpoTrainChain:
             g[name] = (off, w); off += _pad4(w)
         self.gtape_cols, self.g = off, g
         T, MU, VAL, EST = 0, 1, 2, 3          # output slots of the forward launch
-        E, D = cls.ELU, cls.DELU
+        D = fused.grad_code(E)          # the derivative of the same activation from the tape (ELU: cls.ELU / cls.DELU)
         (a1, a2, a3), (c1, c2, c3), (p1, p2), (e1, e2, e3) = ([l for l, _ in st[k]] for k in ("actor", "critic", "priv", "est"))
         ain = t["ain"][0]
         # ---- forward program (what PolicyChain.describe builds for the rollout, plus the saves; the actor's explicit-state columns are the
@@ -251,7 +253,7 @@ class PpoTrainChain:
         b.layer(2, 0, a_w[1], 1, 0, a_w[0], D, a2.weight, None, save=(G, g["a1"][0]), aux=(A, t["a1"][0]), transposed=True)
         b.layer(1, 0, a_w[0], 2, 0, n_in, 0, a1.weight, None, transposed=True)                    # d loss / d actor input (only its latent columns are needed)
         b.load((DP, 0), Z, 0, n_lat)                                                                # the regulariser's gradient at the privileged latent ...
-        b.grad(2, lat_col, Z, 0, n_lat, act=D, aux=(A, ain + lat_col), add=True, save=(G, g["p2"][0]))   # ... + the actor's, times ELU' of the latent
+        b.grad(2, lat_col, Z, 0, n_lat, act=D, aux=(A, ain + lat_col), add=True, save=(G, g["p2"][0]))   # ... + the actor's, times act' of the latent
         b.layer(Z, 0, n_lat, 2, 0, p_w[0], D, p2.weight, None, save=(G, g["p1"][0]), aux=(A, t["p1"][0]), transposed=True)
         b.load((DE, 0), 1, 0, n_exp)
         b.layer(1, 0, n_exp, Z, 0, e_w[1], D, e3.weight, None, save=(G, g["e2"][0]), aux=(A, t["e2"][0]), transposed=True)

@@ -131,7 +131,10 @@ class OnPolicyRunner:
         actor_critic = eval(r["policy_class_name"])(num_actor_obs, num_critic_obs, env.num_actions, num_prop, num_hist,
                                                     ecfg.num_explicit, ecfg.num_latent, ecfg.num_command,
                                                     **self.policy_cfg).to(device)
-        estimator = Estimator(input_dim=num_prop, output_dim=ecfg.num_explicit, hidden_dims=self.estimator_cfg["hidden_dims"]).to(device)
+        # (the reference builds the estimator with ELU whatever policy.activation says, bbc/rsl_rl/runners/on_policy_runner.py:59-60: still the default;
+        # estimator.activation makes it the policy's kind, which the chain launches and the recorded steps require -- fused.uniform_kinds)
+        estimator = Estimator(input_dim=num_prop, output_dim=ecfg.num_explicit, hidden_dims=self.estimator_cfg["hidden_dims"],
+                              activation=self.estimator_cfg.get("activation", "elu")).to(device)
         motion_loader = None
         if self.amp_enabled:
             motion_loader = MotionLoader(device, time_between_frames=env.dt, motion_files_lb=r["motion_files_lb"],

@@ -1,0 +1,391 @@
+"""policy.activation on the fast paths: every activation the reference accepts (bbc/rsl_rl/modules/actor_critic.py:228-245: elu, selu, relu, crelu,
+lrelu, tanh, sigmoid) through the rollout chain launch, the two-launch training chain, the GEMM epilogues and the history encoder's own column sums.
+
+CPU: the descriptions (op lists with the forward / derivative codes of include/qa_sim.h QA_MLP_ACT_*), the recordability gate, and the table's
+"derivative from the layer's OUTPUT" identities in float64.  -m gpu: the kernels against torch in float64.
+
+Bounds of the GPU comparisons: the project's own for the ELU case of the same comparison (test_policy_chain.py: rtol 1e-4, atol 2e-5 forward;
+test_train_chain.py: 3e-4 x max|grad|; test_gemm_layers.py `_tol`), or -- where tanhf / expf against float64 make that too tight -- 3 x the error of
+torch's own fp32 module on the same inputs against float64 (tests/parity_tol.py's 3 x rule), computed in the test (`_allow`)."""
+import copy
+import ctypes as C
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from quadrupedal_agility_amd import _capi
+from quadrupedal_agility_amd.rsl_rl.algorithms import fused, train_chain
+from quadrupedal_agility_amd.rsl_rl.algorithms.fused import PolicyChain
+from quadrupedal_agility_amd.rsl_rl.modules import ActorCritic, Estimator, get_activation
+
+DIMS = dict(num_prop=57, num_hist=10, num_explicit=4, num_latent=29, num_command=11)
+N_OBS = 57 + 4 + 29 + 570 + 11
+# name -> forward code of the chain launches and the GEMM epilogues; the chain's derivative code is the forward code + 3
+CODES = dict(elu=1, relu=2, crelu=2, tanh=3, lrelu=7, selu=8, sigmoid=9)
+NON_ELU = ["relu", "crelu", "lrelu", "selu", "tanh", "sigmoid"]
+NEW = ["tanh", "lrelu", "selu", "sigmoid"]               # what the GEMM epilogues did not evaluate before
+
+
+def modules(name, seed=0, hidden=(512, 256, 128)):
+    """tests/test_policy_chain.py::modules with `activation = name` in the actor-critic and the estimator"""
+    torch.manual_seed(seed)
+    ac = ActorCritic(57 + 4 + 29 + 11, N_OBS, 12, actor_hidden_dims=list(hidden), critic_hidden_dims=list(hidden), priv_encoder_dims=[64],
+                     activation=name, train_with_estimated_latent=True, **DIMS)
+    est = Estimator(57, 4, hidden_dims=[128, 64], activation=name)
+    with torch.no_grad():
+        for p in list(ac.parameters()) + list(est.parameters()):
+            if p.dim() == 1:
+                p.uniform_(-0.2, 0.2)
+    return ac, est
+
+
+class _HostEntryPoints:
+    """libqa_sim.so's host-only entry points under the prefix train_chain's injection point expects from "another library": the descriptions are
+    built on CPU tensors here, and the oracle's twins reject the new codes"""
+
+    def __init__(self):
+        self.lib = _capi.load_library()
+
+    def __getattr__(self, name):
+        assert name.startswith("qo_"), name
+        return getattr(self.lib, "qa_" + name[3:])
+
+
+def _layer_acts(ops):
+    return [op.act for op in ops if op.kind == _capi.MLP_LAYER or op.kind == _capi.MLP_GRAD]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------ CPU
+@pytest.mark.parametrize("name", NON_ELU)
+def test_descriptions_accept_uniform_policies(name):
+    ac, est = modules(name)
+    code = CODES[name]
+    lib = _capi.load_library()
+    for hist in (False, True):
+        chain = PolicyChain.describe(ac, est, True, hist_encoding=hist)
+        assert chain is not None, (name, hist)
+        acts = _layer_acts(chain.ops)
+        # privileged encoder 2 (history encoder 4) + estimator 2 + actor 3 + critic 3 activated layers, three linear outputs (estimate, mean, value)
+        assert sorted(a for a in acts if a) == [code] * (12 if hist else 10) and acts.count(0) == 3, (name, hist, acts)
+        assert lib.qa_mlp_packed_floats(chain.ops, chain.n_ops) == chain.packed_floats
+        strands = (C.c_int32 * chain.n_ops)()
+        assert lib.qa_mlp_strands(chain.ops, chain.n_ops, 4, strands) >= 1, lib.qa_last_error().decode()      # the library's own validation takes the codes
+    tc = train_chain.PpoTrainChain.describe(ac, est, 64, lib=_HostEntryPoints(), prefix="qo_")
+    assert tc is not None, name
+    fwd, bwd = _layer_acts(tc.fwd.ops), _layer_acts(tc.bwd.ops)
+    assert sorted(a for a in fwd if a) == [code] * 10 and fwd.count(0) == 3, (name, fwd)
+    # ten activations -> ten derivative epilogues (nine input-gradient layers + the elementwise op where two gradients meet at the latent); the layer into
+    # the actor's input row has none
+    assert sorted(a for a in bwd if a) == [code + 3] * 10 and bwd.count(0) == 1, (name, bwd)
+    for prog in (tc.fwd, tc.bwd):
+        strands = (C.c_int32 * prog.n_ops)()
+        assert lib.qa_mlp_strands(prog.c_ops, prog.n_ops, 4, strands) >= 1, lib.qa_last_error().decode()
+
+
+def test_descriptions_decline_mixed_stacks_and_other_slopes():
+    ac, est = modules("tanh")
+    ac.actor_trunk[3] = torch.nn.Sigmoid()
+    assert PolicyChain.describe(ac, est, True) is None
+    assert train_chain.PpoTrainChain.describe(ac, est, 64, lib=_HostEntryPoints(), prefix="qo_") is None
+    ac, est = modules("tanh")
+    est2 = Estimator(57, 4, hidden_dims=[128, 64], activation="selu")
+    assert PolicyChain.describe(ac, est2, True) is None and PolicyChain.describe(ac, est2, False) is not None
+    assert train_chain.PpoTrainChain.describe(ac, est2, 64, lib=_HostEntryPoints(), prefix="qo_") is None
+    ac, est = modules("lrelu")
+    ac.critic_trunk[1] = torch.nn.LeakyReLU(0.2)            # not the reference's slope
+    assert PolicyChain.describe(ac, est, True) is None
+    ac, est = modules("elu")
+    ac.history_encoder.activation_fn = torch.nn.Tanh()      # the history encoder counts where it runs
+    assert PolicyChain.describe(ac, est, True) is not None and PolicyChain.describe(ac, est, True, hist_encoding=True) is None
+
+
+def _gate(ac, est):
+    from quadrupedal_agility_amd.rsl_rl.algorithms.gail import SSInfoGAIL
+    stub = types.SimpleNamespace(actor_critic=ac, estimator=est, amp_enabled=False, disc=None, disc_loss_function="MSELoss")
+    return SSInfoGAIL._recordable_networks(stub)
+
+
+@pytest.mark.parametrize("name", NON_ELU)
+def test_recordable_follows_uniformity(name):
+    ac, est = modules(name)
+    assert fused.recordable(ac, est) and _gate(ac, est)
+    assert fused.uniform_activation(ac, est) == CODES[name]
+    ac.actor_trunk[1] = torch.nn.ELU()                      # a mixed stack stays eager
+    assert fused.uniform_activation(ac, est) is None and not _gate(ac, est)
+    ac, est = modules(name)
+    other = Estimator(57, 4, hidden_dims=[128, 64], activation="tanh" if name != "tanh" else "selu")
+    assert not _gate(ac, other)
+
+
+@pytest.mark.parametrize("name", ["elu"] + NON_ELU)
+def test_derivative_from_the_output_equals_autograd(name):
+    g = torch.Generator().manual_seed(11)
+    x = torch.cat([torch.rand(10000, generator=g, dtype=torch.float64) * 12 - 6, torch.zeros(1, dtype=torch.float64)]).requires_grad_(True)
+    m = get_activation(name)
+    y = m(x)
+    (d,) = torch.autograd.grad(y.sum(), x)
+    ours = fused.activation_derivative(CODES[name], y.detach(), 1.0)
+    assert float((ours - d).abs().max()) <= 1e-12, name
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------ GPU
+def _allow(got, ref64, fp32, rtol, atol, tag):
+    """|got - ref64| <= max(project bound, 3 x the largest error of torch's own fp32 evaluation against float64), elementwise"""
+    got, fp32 = got.detach().double().cpu(), fp32.detach().double().cpu()
+    own = 3.0 * float((fp32 - ref64).abs().max())
+    bound = torch.clamp(atol + rtol * ref64.abs(), min=own)
+    err = (got - ref64).abs()
+    print("MEASURED", tag, "max_err=%.3e project_bound_at_worst=%.3e three_x_torch_fp32=%.3e" % (float(err.max()), float((atol + rtol * ref64.abs()).flatten()[err.argmax()]), own))
+    assert bool((err <= bound).all()), (tag, float(err.max()), own)
+
+
+GEMM_SHAPES = [(37, 57, 128, 0), (64, 101, 12, 0), (130, 29, 64, 40), (5, 671, 33, 0),                       # tests/test_gemm_layers.py:46
+               (3684, 98, 512, 0), (1000, 300, 257, 0), (1, 5, 3, 0), (129, 17, 130, 0), (6144, 800, 512, 0)]     # tests/test_gemm_layers.py:80
+
+
+def _case(rows, k, n, seed, extra):
+    g = torch.Generator().manual_seed(seed)
+    xw = torch.randn(rows, k + extra, generator=g)
+    return xw, extra // 2, torch.randn(n, k, generator=g) / k ** 0.5, torch.randn(n, generator=g) * 0.1, torch.randn(rows, n, generator=g)
+
+
+def _gemm_tol(k):
+    return dict(rtol=3e-5, atol=3e-6 * max(1.0, (k / 64) ** 0.5))          # tests/test_gemm_layers.py::_tol
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NEW)
+@pytest.mark.parametrize("rows,k,n,extra", GEMM_SHAPES)
+def test_gemm_epilogues(rows, k, n, extra, name):
+    code = CODES[name]
+    m = get_activation(name)
+    xw, c0, w, b, gy = _case(rows, k, n, rows + k, extra)
+    x = xw[:, c0:c0 + k]
+    ref = m(torch.nn.functional.linear(x.double(), w.double(), b.double()))
+    fp32 = m(torch.nn.functional.linear(x.cuda(), w.cuda(), b.cuda()))
+    xd = xw.cuda()[:, c0:c0 + k]
+    y = fused.linear_forward_raw(xd, w.cuda(), b.cuda(), code)
+    _allow(y, ref, fp32, tag=f"forward {name} {rows}x{k}->{n}", **_gemm_tol(k))
+    if n % 4 == 0:
+        ys = fused.linear_forward_split_raw(xd, w.cuda(), b.cuda(), code)
+        _allow(ys, ref, fp32, tag=f"split forward {name} {rows}x{k}->{n}", **_gemm_tol(k))
+    # (g W) * act'(y_prev): y_prev stands for the previous layer's activation OUTPUT, so it is drawn from the activation's range
+    yprev = m(torch.randn(rows, k, generator=torch.Generator().manual_seed(3)) * 2)
+    d = fused.activation_derivative(code, yprev.double())
+    gin_ref = (gy.double() @ w.double()) * d
+    gin_fp32 = (gy.cuda() @ w.cuda()) * fused.activation_derivative(code, yprev.cuda())
+    gin = fused.linear_backward_input_raw(gy.cuda(), w.cuda(), yprev.cuda(), code)
+    _allow(gin, gin_ref, gin_fp32, tag=f"backward input {name} {rows}x{n}->{k}", **_gemm_tol(n))
+
+
+def _torch_policy(ac, est, obs):
+    with torch.no_grad():
+        x = torch.cat([obs[:, :57], est(obs[:, :57]), obs[:, 61:]], dim=-1)
+        return ac._actor_mean(x, False), ac.evaluate(obs)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NON_ELU)
+@pytest.mark.parametrize("n", [1, 16, 100, 4096])
+def test_rollout_chain(n, name):
+    ac, est = modules(name, seed=3)
+    ac64, est64 = copy.deepcopy(ac).double(), copy.deepcopy(est).double()
+    obs = torch.randn(n, N_OBS) * 1.5
+    rm, rv = _torch_policy(ac64, est64, obs.double())
+    ac, est = ac.cuda(), est.cuda()
+    chain = PolicyChain.describe(ac, est, True)
+    assert chain is not None
+    chain.pack()
+    mean, value = chain.forward(obs.cuda())
+    torch.cuda.synchronize()
+    fm, fv = _torch_policy(ac, est, obs.cuda())
+    _allow(mean, rm, fm, 1e-4, 2e-5, f"rollout chain {name} {n} rows: mean")
+    _allow(value, rv, fv, 1e-4, 2e-5, f"rollout chain {name} {n} rows: value")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["tanh", "lrelu"])
+def test_rollout_chain_history_encoder_variant(name):
+    ac, est = modules(name, seed=5)
+    obs = torch.randn(100, N_OBS)
+    ac64, est64 = copy.deepcopy(ac).double(), copy.deepcopy(est).double()
+    with torch.no_grad():
+        o = obs.double()
+        rm = ac64._actor_mean(torch.cat([o[:, :57], est64(o[:, :57]), o[:, 61:]], dim=-1), True)
+    ac, est = ac.cuda(), est.cuda()
+    chain = PolicyChain.describe(ac, est, True, hist_encoding=True)
+    chain.pack()
+    mean, _ = chain.forward(obs.cuda())
+    with torch.no_grad():
+        g = obs.cuda()
+        fm = ac._actor_mean(torch.cat([g[:, :57], est(g[:, :57]), g[:, 61:]], dim=-1), True)
+    _allow(mean, rm, fm, 1e-4, 2e-5, f"rollout chain (history encoder) {name}")
+
+
+class _PreActivations:
+    """what every activation module of `nets` is given, call by call"""
+
+    def __init__(self, *nets):
+        self.seen = []
+        mods = {id(m): m for net in nets for m in net.modules() if fused.activation_code(m) is not None}
+        self.handles = [m.register_forward_pre_hook(lambda mod, inp: self.seen.append(inp[0].detach().double().cpu())) for m in mods.values()]
+
+    def close(self):
+        for h in self.handles:
+            h.remove()
+        return self.seen
+
+
+def _rows_off_the_kinks(nets64, run64, nets32, run32, rows, tag):
+    """ReLU, LeakyReLU and SELU have a derivative that JUMPS at a zero pre-activation.  Where the float64 pre-activation of some unit is closer to
+    zero than fp32 arithmetic resolves it, "the" derivative is not defined at working precision: any fp32 evaluation -- torch's own, or the
+    kernels' with another summation order -- may land on the other side, and the row's gradient contribution then differs by a whole term, not by
+    rounding (seen: critic_trunk.0.weight of a ReLU policy at 3072 rows off by 1.1613e-7 = 3.8e-4 x max|grad|; that data set has a float64
+    pre-activation of 7.55e-8 in the critic's third layer, where torch's fp32 modules are off by 2.1e-7, and flipping that one unit's mask in the
+    float64 reference moves the gradient by 1.1615e-7).  Such rows say nothing about the gradient
+    arithmetic, so their upstream gradients are zeroed -- for the reference and the code under test alike.  Resolution: 3 x the largest error of
+    torch's own fp32 modules against float64 on that layer's pre-activations (the 3 x rule of tests/parity_tol.py), from the references alone.
+    -> (rows,) bool, True = keep.  Applied to every activation (for the smooth ones it only drops a few rows); at most 4 % of the rows (2 of a small batch) may go."""
+    r64, r32 = _PreActivations(*nets64), _PreActivations(*nets32)
+    with torch.no_grad():
+        run64(); run32()
+    a64, a32 = r64.close(), r32.close()
+    assert len(a64) == len(a32) and len(a64) > 0
+    bad = torch.zeros(rows, dtype=torch.bool)
+    for p64, p32 in zip(a64, a32):
+        tau = 3.0 * float((p32 - p64).abs().max())
+        bad |= (p64.abs() <= tau).reshape(rows, -1).any(dim=1)
+    print("MEASURED", tag, "rows within fp32 resolution of an activation's zero: %d of %d" % (int(bad.sum()), rows))
+    assert int(bad.sum()) <= max(2, rows // 25), (tag, int(bad.sum()))
+    return ~bad
+
+
+def _reference_step(ac, est, obs, g_est, dmu, dvalue, g_priv):
+    """tests/test_train_chain.py::_reference"""
+    for p in list(ac.parameters()) + list(est.parameters()):
+        p.grad = None
+    a = ac.num_prop; b = a + ac.num_explicit; c = b + ac.num_latent
+    value = ac.evaluate(obs)
+    priv = ac.infer_priv_latent(obs[:, b:c])
+    e = est(obs[:, :a])
+    mu = ac._actor_mean(obs, False)
+    torch.autograd.backward([e, mu, value, priv], [g_est, dmu, dvalue.view_as(value), g_priv])
+    return e.detach(), mu.detach(), value.detach(), priv.detach()
+
+
+def _step_inputs(rows, seed):
+    g = torch.Generator().manual_seed(seed)
+    obs = torch.randn(rows, N_OBS, generator=g) * 0.7
+    return obs, torch.randn(rows, 4, generator=g) / rows, torch.randn(rows, 12, generator=g) / rows, torch.randn(rows, generator=g) / rows, torch.randn(rows, 29, generator=g) * 0.1 / rows
+
+
+def _check_grads(named64, named32, got, tag):
+    """every parameter the float64 reference has a gradient for: |g - r| <= max(3e-4 x max|r|, 3 x torch's own fp32 error)"""
+    worst = 0.0
+    for (name, p), (_, p32), q in zip(named64, named32, got):
+        if p.grad is None:
+            continue
+        assert q.grad is not None, (tag, name)
+        r = p.grad
+        scale = float(r.abs().max()) + 1e-300
+        own = 3.0 * float((p32.grad.double().cpu() - r).abs().max())
+        err = float((q.grad.detach().double().cpu() - r).abs().max())
+        worst = max(worst, err / scale)
+        assert err <= max(3e-4 * scale, own), (tag, name, err, scale, own)
+    print("MEASURED", tag, "worst max|g - r| / max|r| = %.3e" % worst)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NON_ELU)
+@pytest.mark.parametrize("rows", [48, 3072])
+def test_training_chain(rows, name):
+    ac, est = modules(name, seed=3)
+    ac64, est64 = copy.deepcopy(ac).double(), copy.deepcopy(est).double()
+    ac32, est32 = copy.deepcopy(ac), copy.deepcopy(est)
+    ac, est = ac.cuda(), est.cuda()
+    ins = _step_inputs(rows, seed=rows)
+    a, b = ac.num_prop + ac.num_explicit, ac.num_prop + ac.num_explicit + ac.num_latent
+    fwd = lambda m, e, o: (m.evaluate(o), m.infer_priv_latent(o[:, a:b]), e(o[:, :ac.num_prop]), m._actor_mean(o, False))
+    keep = _rows_off_the_kinks((ac64, est64), lambda: fwd(ac64, est64, ins[0].double()), (ac32, est32), lambda: fwd(ac32, est32, ins[0]), rows,
+                               f"training chain {name} {rows} rows")
+    ins = (ins[0],) + tuple(t * (keep[:, None] if t.dim() == 2 else keep) for t in ins[1:])
+    refs = _reference_step(ac64, est64, *[t.double() for t in ins])
+    fp32 = _reference_step(ac32, est32, *ins)
+    chain = train_chain.PpoTrainChain.describe(ac, est, rows)
+    assert chain is not None
+    chain.pack()
+    dv = [t.cuda() for t in ins]
+    outs = chain.forward(dv[0])
+    torch.cuda.synchronize()
+    for got, r, f, tag in zip(outs, refs, fp32, ("est", "mu", "value", "priv")):
+        _allow(got, r, f, 1e-4, 2e-5, f"training chain {name} {rows} rows: {tag}")
+    chain.backward(*dv[1:], defer=False)
+    torch.cuda.synchronize()
+    named64 = list(ac64.named_parameters()) + list(est64.named_parameters())
+    named32 = list(ac32.named_parameters()) + list(est32.named_parameters())
+    got = list(ac.parameters()) + list(est.parameters())
+    _check_grads(named64, named32, got, f"training chain {name} {rows} rows")
+    # in parts, finished by the one reduction launch: the same gradients
+    for p in got:
+        p.grad = None
+    chain.forward(dv[0])
+    chain.backward(*dv[1:], defer=True)
+    assert fused.pending_grads() == 26
+    fused.flush_pending_grads()
+    torch.cuda.synchronize()
+    _check_grads(named64, named32, got, f"training chain {name} {rows} rows, in parts")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["tanh", "selu"])
+def test_mlp_chain_at_full_size(name):
+    """the critic stack at a 24,576-row minibatch, 671 -> 512 -> 256 -> 128 -> 1: every layer on the hand-written GEMMs, whatever `own_layer` says"""
+    rows = 24576
+    ac, _ = modules(name, seed=7)
+    trunk, head = ac.critic_trunk, ac.critic_head
+    t64, h64 = copy.deepcopy(trunk).double(), copy.deepcopy(head).double()
+    t32, h32 = copy.deepcopy(trunk).cuda(), copy.deepcopy(head).cuda()
+    trunk, head = trunk.cuda(), head.cuda()
+    g = torch.Generator().manual_seed(2)
+    x, gy = torch.randn(rows, N_OBS, generator=g) * 0.7, torch.randn(rows, 1, generator=g) / rows
+    t32c = copy.deepcopy(t64).float()
+    gy = gy * _rows_off_the_kinks((t64,), lambda: t64(x.double()), (t32c,), lambda: t32c(x), rows, f"_MlpChain {name}")[:, None]
+    y64 = h64(t64(x.double())); y64.backward(gy.double())
+    y32 = h32(t32(x.cuda())); y32.backward(gy.cuda())
+    y = fused.mlp_chain([trunk, head], x.cuda())
+    assert type(y.grad_fn).__name__.startswith("_MlpChain") and not [f for f, _ in y.grad_fn.next_functions if f is not None and "MlpChain" in type(f).__name__]
+    fused.assert_recordable_graph([y], "critic stack")
+    y.backward(gy.cuda())
+    torch.cuda.synchronize()
+    _allow(y, y64.detach(), y32, 1e-4, 2e-5, f"_MlpChain {name} forward")
+    named64 = list(t64.named_parameters()) + list(h64.named_parameters())
+    named32 = list(t32.named_parameters()) + list(h32.named_parameters())
+    _check_grads(named64, named32, list(trunk.parameters()) + list(head.parameters()), f"_MlpChain {name} 24576 rows")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["tanh", "lrelu", "relu"])
+def test_history_encoder_bias_gradients_are_our_column_sums(name):
+    """the history encoder under autograd: no torch batch reduction in its graph, gradients equal to float64 autograd"""
+    ac, _ = modules(name, seed=9)
+    he = ac.history_encoder
+    he64, he32 = copy.deepcopy(he).double(), copy.deepcopy(he).cuda()
+    he = he.cuda()
+    g = torch.Generator().manual_seed(4)
+    rows = 6144
+    x, gy = torch.randn(rows, 10, 57, generator=g), torch.randn(rows, 29, generator=g) / rows
+    he32c = copy.deepcopy(he64).float()
+    gy = gy * _rows_off_the_kinks((he64,), lambda: he64(x.double()), (he32c,), lambda: he32c(x), rows, f"history encoder {name}")[:, None]
+    he64(x.double()).backward(gy.double())
+    fused.ENABLED = False
+    try:
+        he32(x.cuda()).backward(gy.cuda())
+    finally:
+        fused.ENABLED = True
+    y = he(x.cuda())
+    fused.assert_recordable_graph([y], "history encoder")
+    y.backward(gy.cuda())
+    torch.cuda.synchronize()
+    _check_grads(list(he64.named_parameters()), list(he32.named_parameters()), list(he.parameters()), f"history encoder {name}")
