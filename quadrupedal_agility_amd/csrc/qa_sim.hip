@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "../../include/qa_sim.h"
+#include "../../include/qa_sim_curriculum.h"
 #include "qa_go2_model.h"
 #include "qa_physics.h"
 
@@ -94,6 +95,12 @@ struct Ptrs {
     float *obst_desc, *obst_state;
     int64_t *reset, *episode_length;
     uint8_t *time_out, *last_contacts, *contact_filt;
+    // qa_set_terrain_curriculum (include/qa_sim_curriculum.h): caller-owned buffers, not arena tensors; all null = curriculum off
+    int64_t *terrain_levels;
+    const int64_t *terrain_types;
+    const float *terrain_origins;
+    int32_t terrain_rows, terrain_cols;
+    float terrain_env_length, terrain_episode_s;
 };
 
 struct qa_sim {
@@ -205,11 +212,40 @@ __device__ __forceinline__ void mocap_slerp(const float *q0, const float *q1, fl
     for (int i = 0; i < 4; ++i) out[i] = (same || tiny) ? q0[i] : (at_one ? q1[i] : (at_zero ? q0[i] : q0[i] * w0 + q1[i] * w1));
 }
 
-// reset of one env by its quad (legged_robot.py:178-240).  Updates st and the command/latent registers.
+// _update_terrain_curriculum (legged_robot.py:689-711) of one resetting env, executed redundantly by the 4 lanes of its quad so that each of
+// them holds the new origin in registers (`org`: in = the origin the episode ran on, out = the origin to spawn at); lane 0 stores the level
+// and the ENV_ORIGINS row.  `pos` and `cmd` are the episode's last root position and commands (reset_idx :190-192 runs before :202 resamples).
+// Every lane's loads of the level and of the origin row are issued before lane 0's stores to them (one wavefront, program order).
+// A level past the last row is redrawn uniformly (:707-710, torch.randint_like there; the handle's Philox stream here).
+__device__ __forceinline__ void update_terrain_level(const qa_config &c, const Ptrs &p, int env, int leg, bool valid, int64_t step, const V3 &pos,
+                                                     const float cmd[5], float org[3]) {
+    const float dx = pos.x - org[0], dy = pos.y - org[1];
+    const float dist = sqrtf(dx * dx + dy * dy);
+    const bool up = dist > p.terrain_env_length / 2;
+    const bool down = (dist < sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]) * p.terrain_episode_s * 0.5f) && !up;
+    const int rows = p.terrain_rows, cols = p.terrain_cols;
+    int64_t level = p.terrain_levels[env] + (up ? 1 : 0) - (down ? 1 : 0);
+    if (level >= rows) {
+        const F4 u = rng4(c.seed, env + c.env_id_offset, step, RS_TERRAIN_LEVEL, 0);
+        level = min((int)(u.v[0] * (float)rows), rows - 1);
+    } else if (level < 0) level = 0;
+    int64_t type = p.terrain_types[env];
+    type = type < 0 ? 0 : (type >= cols ? cols - 1 : type);          // a bad type must not index past the table
+    const float *o = p.terrain_origins + (level * cols + type) * 3;
+    org[0] = o[0]; org[1] = o[1]; org[2] = o[2];
+    if (leg == 0 && valid) {
+        p.terrain_levels[env] = level;
+        p.env_origins[3 * env] = org[0]; p.env_origins[3 * env + 1] = org[1]; p.env_origins[3 * env + 2] = org[2];
+    }
+}
+
+// reset of one env by its quad (legged_robot.py:178-240).  Updates st and the command/latent registers.  ORG: spawn at `org` (the
+// caller holds the origin in registers: the terrain curriculum may just have moved it) instead of at the env's ENV_ORIGINS row.
+template <bool ORG = false>
 __device__ __forceinline__ void reset_env(const qa_config &c, const Ptrs &p, const MocapIdx &mi, int env, int leg, int64_t step,
-                                          EnvState &st, float cmd[5], float &eps, int &gait) {
+                                          EnvState &st, float cmd[5], float &eps, int &gait, const float *org = nullptr) {
     resample_commands(c, p.prior, env, step, RS_CMD_RESET, cmd, eps, gait);
-    const float ox = p.env_origins[3 * env], oy = p.env_origins[3 * env + 1], oz = p.env_origins[3 * env + 2];
+    const float ox = ORG ? org[0] : p.env_origins[3 * env], oy = ORG ? org[1] : p.env_origins[3 * env + 1], oz = ORG ? org[2] : p.env_origins[3 * env + 2];
     if (c.reset_mode == 1 && mi.on) {
         // MotionLoader.get_full_frame_batch (motion_loader.py:461-474): clip ~ MotionWeight inside the gait, time ~ U over the
         // clip's sampling range, the two bracketing frames blended (get_full_frame_at_time_batch :410-447); index arithmetic in
@@ -574,7 +610,13 @@ __device__ __forceinline__ void post_physics_phase(const qa_config &c, const Ptr
                 esum[r] = 0.f;
             }
             if (leg == 0 && valid) atomicAdd(&p.episode_stats[16 * (step & 1) + 14], 1.0f);
-            reset_env(c, p, mi, env, leg, step, st, cmd, eps, gait);
+            if (!PLANE) {
+                float org[3] = {p.env_origins[3 * env], p.env_origins[3 * env + 1], p.env_origins[3 * env + 2]};
+                if (p.terrain_levels) update_terrain_level(c, p, env, leg, valid, step, st.pos, cmd, org);      // uniform over the launch
+                reset_env<true>(c, p, mi, env, leg, step, st, cmd, eps, gait, org);
+            } else {
+                reset_env(c, p, mi, env, leg, step, st, cmd, eps, gait);
+            }
             cmd_dirty = true;
             epl = 0;
             lav = st.vw; law = st.ww;
@@ -1367,6 +1409,7 @@ static void fill_ptrs(qa_sim *s) {
     p.rbstate = (float *)(a + L.off[QA_T_RIGID_BODY_STATE]);
     p.mocap_clips = (double *)(a + L.off[QA_T_MOCAP_CLIPS]);
     p.ticket = (int32_t *)(a + L.off[QA_T_STEP_TICKET]);
+    p.terrain_levels = nullptr; p.terrain_types = nullptr; p.terrain_origins = nullptr; p.terrain_rows = p.terrain_cols = 0; p.terrain_env_length = p.terrain_episode_s = 0.f;
 }
 
 static void build_table(float *t) {
@@ -1489,6 +1532,23 @@ static void launch_env_step(qa_sim *s, const StepArgs &a, hipStream_t st) {
 int qa_set_lean_exports(qa_sim *s, int32_t mask) {
     if (!s || (mask != 0 && mask != 1 && mask != 3)) { snprintf(g_err, sizeof(g_err), "qa_set_lean_exports: mask must be 0, 1 or 3"); return QA_E_ARG; }
     s->lean = mask;
+    return QA_OK;
+}
+
+int qa_set_terrain_curriculum(qa_sim *s, int64_t *terrain_levels, const int64_t *terrain_types, const float *terrain_origins, int32_t rows, int32_t cols,
+                              float env_length, float max_episode_length_s) {
+    if (!s) return QA_E_ARG;
+    if (s->cfg.terrain_type != 1) { snprintf(g_err, sizeof(g_err), "qa_set_terrain_curriculum: the handle has no height field (terrain_type != 1)"); return QA_E_ARG; }
+    Ptrs &p = s->p;
+    if (!terrain_levels && !terrain_types && !terrain_origins) {
+        p.terrain_levels = nullptr; p.terrain_types = nullptr; p.terrain_origins = nullptr; p.terrain_rows = p.terrain_cols = 0; p.terrain_env_length = p.terrain_episode_s = 0.f;
+        return QA_OK;
+    }
+    if (!terrain_levels || !terrain_types || !terrain_origins || rows <= 0 || cols <= 0) {
+        snprintf(g_err, sizeof(g_err), "qa_set_terrain_curriculum: three device buffers and rows, cols > 0 (or three NULLs to switch it off)"); return QA_E_ARG;
+    }
+    p.terrain_levels = terrain_levels; p.terrain_types = terrain_types; p.terrain_origins = terrain_origins;
+    p.terrain_rows = rows; p.terrain_cols = cols; p.terrain_env_length = env_length; p.terrain_episode_s = max_episode_length_s;
     return QA_OK;
 }
 

@@ -221,6 +221,15 @@ class LeggedRobot:
         self.max_terrain_level = self.cfg.terrain.num_rows
         self.terrain_origins = torch.from_numpy(t.env_origins).to(dev).to(torch.float)
         self.env_origins.copy_(self.terrain_origins[self.terrain_levels, self.terrain_types])
+        if self.cfg.terrain.curriculum:
+            # _update_terrain_curriculum (legged_robot.py:689-711) runs inside the step's reset path, on THESE tensors: they are handed over
+            # once and never rebound, so `terrain_levels` stays the live tensor the reference's attribute is
+            if not hasattr(self.sim, "set_terrain_curriculum"):
+                raise NotImplementedError("terrain.curriculum needs the HIP engine (qa_set_terrain_curriculum); this backend has no twin of it")
+            self.terrain_levels = self.terrain_levels.to(torch.long).contiguous()
+            self.terrain_types = self.terrain_types.contiguous()
+            self.terrain_origins = self.terrain_origins.contiguous()
+            self.sim.set_terrain_curriculum(self.terrain_levels, self.terrain_types, self.terrain_origins, t.env_length, self.max_episode_length_s)
 
     def _get_heights(self, env_ids=None):
         """The reference's 187-point height scan (legged_robot.py:1190-1228) for callers that want all of it; the
@@ -350,6 +359,8 @@ class LeggedRobot:
             self._episode_means.copy_(torch.where(cnt > 0, mean, self._episode_means))
             snap = self._episode_means.clone()
         self.extras["episode"] = {"rew_" + n: snap[_capi.REWARD_NAMES.index(n)] for n in self.reward_names}
+        if self.cfg.terrain.curriculum:     # :235-236; the levels are the tensor the step just updated, the mean stays on the device
+            self.extras["episode"]["terrain_level"] = torch.mean(self.terrain_levels.float())
         if self.cfg.env.send_timeouts:
             self.extras["time_outs"] = self.time_out_buf
 

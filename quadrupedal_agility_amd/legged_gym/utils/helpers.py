@@ -92,6 +92,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
                 setattr(_node(env_cfg, node), field, int(v) if arg in ("disc_history_len", "disc_obs_len") else v)
         if getattr(args, "terrain", None) is not None:
             env_cfg.terrain.mesh_type = args.terrain
+        if getattr(args, "terrain_curriculum", False):
+            env_cfg.terrain.curriculum = True
         if getattr(args, "no_mocap_init", False):
             env_cfg.env.mocap_state_init = False
     if cfg_train is not None:
@@ -137,6 +139,7 @@ def get_args(argv=None):
     p.add_argument("--num_threads", type=int, default=0)
     p.add_argument("--physics_engine", default="qa")
     p.add_argument("--terrain", type=str, default=None, help="override terrain.mesh_type: plane | heightfield | trimesh")
+    p.add_argument("--terrain_curriculum", action="store_true", help="terrain.curriculum = True: resetting envs move between the course's difficulty rows (heightfield | trimesh)")
     p.add_argument("--no_amp", action="store_true", help="disable the discriminator (BASELINE config 2)")
     p.add_argument("--no_mocap_init", action="store_true", help="reset from the default pose instead of mocap frames")
     p.add_argument("--log_root", type=str, default="default")

@@ -530,7 +530,10 @@ class OnPolicyRunner:
         if locs["ep_infos"]:
             for key in locs["ep_infos"][0]:
                 vals = torch.stack([torch.as_tensor(e[key], device=self.device).reshape(()) for e in locs["ep_infos"]])
-                w.add_scalar("Episode/" + key, (vals.mean() / self.env.reward_scales[key[4:]]).item(), it)
+                # "rew_<term>" is divided by the term's scale (on_policy_runner.py:253); any other key ("terrain_level") is written as it is --
+                # the reference divides those too and raises KeyError on them
+                scale = self.env.reward_scales[key[4:]] if key.startswith("rew_") else 1.0
+                w.add_scalar("Episode/" + key, (vals.mean() / scale).item(), it)
         for tag, v in zip(self._LOSS_TAGS, locs["losses"][:13]):
             w.add_scalar("Loss/" + tag, v, it)
         w.add_scalar("Loss/hist_latent_loss", locs["mean_hist_latent_loss"], it)

@@ -70,6 +70,23 @@ class QaSim:
         _check(self.lib.qa_set_lean_exports(self.h, int(mask)), self.lib, "qa_set_lean_exports")
         self.lean_exports = int(mask)
 
+    def set_terrain_curriculum(self, terrain_levels, terrain_types, terrain_origins, env_length, max_episode_length_s):
+        """qa_set_terrain_curriculum (include/qa_sim_curriculum.h): from now on the step's reset path moves resetting envs between the rows
+        of `terrain_origins` (rows, cols, 3), rewriting `terrain_levels` (N) int64 and ENV_ORIGINS in place.  The handle keeps the POINTERS
+        (and this object the tensors, so that they stay alive): call it before a rollout is recorded.  Three Nones switch it off."""
+        if terrain_levels is None and terrain_types is None and terrain_origins is None:
+            _check(self.lib.qa_set_terrain_curriculum(self.h, None, None, None, 0, 0, 0.0, 0.0), self.lib, "qa_set_terrain_curriculum")
+            self._curriculum = None
+            return
+        n = self.cfg.num_envs
+        for x, dt, shape in ((terrain_levels, torch.int64, (n,)), (terrain_types, torch.int64, (n,))):
+            assert x.is_cuda and x.dtype == dt and x.is_contiguous() and tuple(x.shape) == shape
+        o = terrain_origins
+        assert o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and o.dim() == 3 and o.shape[2] == 3
+        _check(self.lib.qa_set_terrain_curriculum(self.h, terrain_levels.data_ptr(), terrain_types.data_ptr(), o.data_ptr(), int(o.shape[0]), int(o.shape[1]),
+                                                  float(env_length), float(max_episode_length_s)), self.lib, "qa_set_terrain_curriculum")
+        self._curriculum = (terrain_levels, terrain_types, terrain_origins)
+
     def step_dev(self, actions, delay, step_counter):
         """qa_env_step_dev: the step counter lives in device memory (graph-replayable)."""
         assert actions.is_cuda and actions.dtype == torch.float32 and actions.is_contiguous()
