@@ -235,7 +235,24 @@ def bind_extensions(lib, prefix="qa_"):
     no oracle twin, not part of ABI_SYMBOLS."""
     # include/qa_sim_curriculum.h
     f = getattr(lib, prefix + "set_terrain_curriculum"); f.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_float, C.c_float]; f.restype = C.c_int
+    # include/qa_tsc_curriculum.h
+    f = getattr(lib, prefix + "tsc_obstacle_curriculum"); f.argtypes = [C.POINTER(QaTscObstCurr), C.c_void_p]; f.restype = C.c_int
     return lib
+
+
+class QaTscObstCurr(C.Structure):
+    """qa_tsc_obst_curr of include/qa_tsc_curriculum.h"""
+    _fields_ = [("step_counter", C.c_void_p), ("counter_offset", C.c_void_p), ("success_rate", C.c_void_p), ("any_reset", C.c_void_p),
+                ("threshold", C.c_double), ("period", C.c_int64), ("state", C.c_void_p), ("ticket", C.c_void_p), ("increments", C.c_void_p),
+                ("biases", C.c_void_p), ("last", C.c_int32), ("reserved", C.c_int32),
+                ("cell_index", C.c_void_p), ("cell_kind", C.c_void_p), ("cell_base", C.c_void_p), ("num_cells", C.c_int64),
+                ("height_samples", C.c_void_p), ("scan_samples", C.c_void_p), ("map_cells", C.c_int64),
+                ("ceiling_index", C.c_void_p), ("ceiling_base", C.c_void_p), ("num_ceiling_cells", C.c_int64), ("ceiling_samples", C.c_void_p),
+                ("goal_index", C.c_void_p), ("goal_kind", C.c_void_p), ("goal_base", C.c_void_p), ("num_goal_entries", C.c_int64),
+                ("env_goals", C.c_void_p), ("goal_floats", C.c_int64)]
+
+
+TSC_OBST_BAR, TSC_OBST_TYRE, TSC_OBST_STATE_WORDS = 0, 1, 4
 
 
 class QaMlpOp(C.Structure):
@@ -359,8 +376,8 @@ class QaTscDepthIo(C.Structure):
 ABI_SYMBOLS = ["arena_bytes", "create", "destroy", "tensor_info", "env_step", "env_step_dev", "reset_all", "simulate",
                "set_mocap", "debug_post_physics", "env_physics_step", "tsc_reset", "tsc_reset_dev", "simulate_if", "gae", "ppo_loss", "ppo_loss_scratch_bytes", "hybrid_ppo_loss", "hybrid_ppo_loss_scratch_bytes", "elu_backward_bias",
                "elu_backward_bias_scratch_bytes", "narrow_wgrad", "narrow_wgrad_scratch_bytes", "linear_forward", "linear_backward_input", "linear_backward_weight", "linear_backward_weight_scratch_bytes", "linear_backward_weight_layout", "linear_backward_weight_batch", "linear_backward_weight_batch_layout", "linear_backward_weight_batch_scratch_bytes", "slab_sum", "linear_forward_split", "linear_forward_split_scratch_bytes", "depth_stem_forward", "depth_stem_backward", "depth_stem_backward_scratch_bytes", "conv_nhwc_forward", "conv_nhwc_backward_input", "conv_nhwc_backward_weight", "conv_nhwc_backward_weight_scratch_bytes", "elu_backward_pad", "normalizer_update", "normalizer_apply", "clip_adam_step", "clip_adam_step_hostgrads", "clip_adam_step_reduce", "clip_adam_pair_step", "grad_reduce", "adam_stack_step", "rollout_act", "rollout_act_store", "rollout_act_hybrid", "rollout_post", "rollout_post_amp", "disc_loss", "disc_loss_logits", "disc_loss_scratch_bytes", "disc_prepare", "disc_sample_prepare", "disc_step_tail", "disc_step_tail_scratch_bytes", "pair_loss", "pair_loss_scratch_bytes", "pair_losses", "pair_losses_scratch_bytes", "accumulate_scalars", "gather_rows", "kl_lr_rule", "episode_means", "set_lean_exports", "mlp_packed_floats", "mlp_pack", "mlp_forward", "mlp_strands", "mlp_groups", "mlp_set_groups", "tsc_set_commands", "tsc_goal_step", "tsc_observations", "tsc_depth_update", "tsc_reset_stats", "tsc_push", "tsc_start_pose", "tsc_reset_where", "last_error", "abi_version"]
-# include/qa_sim_curriculum.h (bind_extensions)
-EXTENSION_SYMBOLS = ["set_terrain_curriculum"]
+# include/qa_sim_curriculum.h, include/qa_tsc_curriculum.h (bind_extensions)
+EXTENSION_SYMBOLS = ["set_terrain_curriculum", "tsc_obstacle_curriculum"]
 
 _LIB = None
 # QA_LIB: another build of the SAME library (A/B measurements of a kernel variant, tools/r5_call.sh); there is still no fallback -- a missing file raises

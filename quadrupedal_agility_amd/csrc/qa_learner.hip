@@ -15,6 +15,7 @@
 #include <stdio.h>
 
 #include "../../include/qa_sim.h"
+#include "../../include/qa_tsc_curriculum.h"
 #include "qa_device.h"
 
 namespace {
@@ -1035,6 +1036,48 @@ __global__ void __launch_bounds__(64) qa_tsc_reset_where_kernel(ResetWhereArgs a
     }
 }
 
+/* the obstacle curriculum of the task-level course (include/qa_tsc_curriculum.h): the decision is a uniform read that every workgroup makes for itself;
+ * on the rare raising step the grid walks the compact lists of movable cells / goal entries, and the last workgroup to finish publishes the new state */
+constexpr int OBST_CURR_BLOCK = 256;
+__global__ void __launch_bounds__(OBST_CURR_BLOCK) qa_tsc_obstacle_curriculum_kernel(qa_tsc_obst_curr a) {
+    __shared__ int64_t s_count;
+    const int64_t gc = *a.step_counter - *a.counter_offset;
+    if (!(a.any_reset[0] != 0 && gc % a.period == 0 && *a.success_rate > a.threshold)) return;
+    if (threadIdx.x == 0) s_count = a.state[0] + 1;
+    __syncthreads();
+    const int64_t count = s_count;
+    const int k = (int)(count < 0 ? 0 : (count > (int64_t)a.last ? (int64_t)a.last : count));
+    const int inc[2] = {a.increments[2 * k], a.increments[2 * k + 1]};
+    const double bias[2] = {a.biases[2 * k], a.biases[2 * k + 1]};
+    const int64_t stride = (int64_t)gridDim.x * OBST_CURR_BLOCK, t0 = (int64_t)blockIdx.x * OBST_CURR_BLOCK + threadIdx.x;
+    for (int64_t i = t0; i < a.num_cells; i += stride) {
+        const int64_t c = a.cell_index[i];
+        if (c < 0 || c >= a.map_cells) continue;
+        const int16_t v = (int16_t)((int)a.cell_base[i] + inc[a.cell_kind[i] ? 1 : 0]);
+        a.height_samples[c] = v;
+        if (a.scan_samples) a.scan_samples[c] = v;
+    }
+    for (int64_t i = t0; i < a.num_ceiling_cells; i += stride) {
+        const int64_t c = a.ceiling_index[i];
+        if (c < 0 || c >= a.map_cells) continue;
+        a.ceiling_samples[c] = (int16_t)((int)a.ceiling_base[i] + inc[1]);
+    }
+    for (int64_t i = t0; i < a.num_goal_entries; i += stride) {
+        const int64_t g = a.goal_index[i];
+        if (g < 0 || g >= a.goal_floats) continue;
+        a.env_goals[g] = (float)(a.goal_base[i] + bias[a.goal_kind[i] ? 1 : 0]);
+    }
+    __syncthreads();                                   // thread 0 read state[0] before this workgroup takes its ticket
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(a.ticket, 1) == (int)gridDim.x - 1) {
+            *a.ticket = 0;
+            a.state[0] = count; a.state[1] = __double_as_longlong(bias[0]); a.state[2] = __double_as_longlong(bias[1]); a.state[3] = gc;
+            __threadfence();
+        }
+    }
+}
+
 constexpr int RS_ACT_CHOICE = 21;
 struct HybridActArgs {
     const float *logits, *mean, *std, *value;
@@ -1952,6 +1995,25 @@ int qa_tsc_reset_where(const uint8_t *flags, const uint8_t *any_reset, const int
     hipLaunchKernelGGL(qa_tsc_reset_where_kernel, dim3((unsigned)((num_envs + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_lerr, sizeof(g_lerr), "qa_tsc_reset_where: %s", hipGetErrorString(e)); return QA_E_DEVICE; }
+    return QA_OK;
+}
+
+int qa_tsc_obstacle_curriculum(const qa_tsc_obst_curr *args, void *stream) {
+    if (!args) { snprintf(g_lerr, sizeof(g_lerr), "qa_tsc_obstacle_curriculum: null argument"); return QA_E_ARG; }
+    const qa_tsc_obst_curr &a = *args;
+    if (!a.step_counter || !a.counter_offset || !a.success_rate || !a.any_reset || !a.state || !a.ticket || !a.increments || !a.biases || a.period <= 0 || a.last < 0 ||
+        a.num_cells < 0 || a.num_ceiling_cells < 0 || a.num_goal_entries < 0 || a.map_cells < 0 || a.goal_floats < 0 ||
+        (a.num_cells > 0 && (!a.cell_index || !a.cell_kind || !a.cell_base || !a.height_samples)) ||
+        (a.num_ceiling_cells > 0 && (!a.ceiling_index || !a.ceiling_base || !a.ceiling_samples)) ||
+        (a.num_goal_entries > 0 && (!a.goal_index || !a.goal_kind || !a.goal_base || !a.env_goals))) {
+        snprintf(g_lerr, sizeof(g_lerr), "qa_tsc_obstacle_curriculum: missing pointer, period <= 0, last < 0 or a negative length"); return QA_E_ARG; }
+    int64_t most = a.num_cells > a.num_ceiling_cells ? a.num_cells : a.num_ceiling_cells;
+    if (a.num_goal_entries > most) most = a.num_goal_entries;
+    int64_t blocks = (most + OBST_CURR_BLOCK - 1) / OBST_CURR_BLOCK;
+    blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);          // a function of the list lengths only: the same geometry on every step
+    hipLaunchKernelGGL(qa_tsc_obstacle_curriculum_kernel, dim3((unsigned)blocks), dim3(OBST_CURR_BLOCK), 0, (hipStream_t)stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_lerr, sizeof(g_lerr), "qa_tsc_obstacle_curriculum: %s", hipGetErrorString(e)); return QA_E_DEVICE; }
     return QA_OK;
 }
 

@@ -108,6 +108,8 @@ class Obstacle:
         # not in the reference: the undersides of the two overhanging obstacles (tunnel roof, upper arc of the tyre) on the same
         # grid, for this build's physics (QA_T_CEILING_SAMPLES) -- the reference collides with the obstacle meshes instead
         self.ceiling_raw = np.full((self.tot_rows, self.tot_cols), NO_CEILING, dtype=np.int16)
+        # which ceiling cells are the tyre's upper arc (the tunnel roof shares the field): the obstacle curriculum lifts these with the tyre
+        self.tire_ceiling_mask = np.zeros((self.tot_rows, self.tot_cols), dtype=bool)
 
         xx, yy = np.meshgrid(np.arange(self.num_rows), np.arange(self.num_cols))
         self.spacing_x, self.spacing_y, self.env_boarder = cfg.env_length, cfg.env_width, cfg.env_boarder
@@ -267,6 +269,7 @@ class Obstacle:
             tile_c = np.full(shape, NO_CEILING, dtype=np.int16)
             tile_e = np.zeros(shape, dtype=np.int16)
             tile_goals = np.zeros((self.num_obst_per_env, self.num_goals, 3))
+            tyre_c = np.full(shape, NO_CEILING, dtype=np.int16)
             for j, kind in enumerate(order):
                 idx = self.obst_types.index(kind)
                 rx = cfg.random_x[kind]
@@ -301,9 +304,11 @@ class Obstacle:
                 self.add_border(new_h)
                 tile_h |= new_h
                 tile_c = np.minimum(tile_c, new_c)
+                if kind == "tire_jump":
+                    tyre_c = new_c
                 tile_e |= new_e.astype(np.int16)
                 tile_goals[j] = t.goals
-            self.add_terrain_to_map(tile_h, tile_e, tile_goals, i, tile_c)
+            self.add_terrain_to_map(tile_h, tile_e, tile_goals, i, tile_c, (tyre_c != NO_CEILING) & (tile_c == tyre_c))
         # the movable parts were drawn 1 m (bar) / 10 m (tyre) below ground so that they can be told apart in the map
         vs = self.vertical_scale
         self.bar_jump_mask = (self.height_field_raw > int(-5 / vs)) & (self.height_field_raw < 0)
@@ -315,7 +320,7 @@ class Obstacle:
         self.env_goals[self.bar_jump_goal_mask] -= self.bar_jump_joint_bias
         self.env_goals[self.tire_jump_goal_mask] -= self.tire_jump_joint_bias
 
-    def add_terrain_to_map(self, tile_h, tile_e, tile_goals, i, tile_c=None):
+    def add_terrain_to_map(self, tile_h, tile_e, tile_goals, i, tile_c=None, tile_tyre_c=None):
         hs = self.horizontal_scale
         sx = int(self.border + self.env_origins[i, 0] / hs)
         sy = int(self.border + self.env_origins[i, 1] / hs)
@@ -325,6 +330,8 @@ class Obstacle:
         self.x_edge_mask[sx:ex, sy:ey] = tile_e
         if tile_c is not None:
             self.ceiling_raw[sx:ex, sy:ey] = tile_c
+        if tile_tyre_c is not None:
+            self.tire_ceiling_mask[sx:ex, sy:ey] = tile_tyre_c
         self.env_goals[i] = tile_goals + np.array([self.env_origins[i, 0], self.env_origins[i, 1], 0])
 
     # ------------------------------------------------------------------ what the env turns the arrays into

@@ -319,11 +319,15 @@ class OnPolicyRunner:
         buffers = {k: deque(maxlen=1000) for k in keys}
         reach_goal_buffer = deque(maxlen=1000)
         logging = self.log_dir is not None
+        # obstacle curriculum of a data-parallel job: one course, so all ranks raise on the same step -- every rank keeps its reach-goal window
+        # (logging or not) and sets success_rate from the job's (sum, count)
+        shared_rate = bool(getattr(env, "obstacle_curriculum_armed", False)) and self.distributed and dist.get_world_size() > 1
+        track = logging or shared_rate
         tot_iter = self.current_learning_iteration + num_learning_iterations
         for it in range(self.current_learning_iteration, tot_iter):
             start = time.time()
             hist_encoding = it % self.dagger_update_freq == 0
-            ep_infos = self._collect(hist_encoding, logging)
+            ep_infos = self._collect(hist_encoding, track)
             collection_time = time.time() - start
             start = time.time()
             with torch.inference_mode():
@@ -331,15 +335,20 @@ class OnPolicyRunner:
             losses = alg.update()
             mean_hist_latent_loss = alg.update_dagger() if hist_encoding else 0.0
             learn_time = time.time() - start
-            if logging:            # ONE host read per iteration for the episode statistics
+            if track:              # ONE host read per iteration for the episode statistics
                 rs = self._rs
                 masks = rs["fin_masks"]
                 sel = rs["fin_vals"].permute(0, 2, 1)[masks].cpu()
                 for i, k in enumerate(keys):
                     buffers[k].extend(sel[:, i].tolist())
                 reach_goal_buffer.extend(rs["fin_reach"][masks].float().cpu().tolist())
-                if len(reach_goal_buffer) > 0:
+                if shared_rate:
+                    rate = self._job_success_rate(reach_goal_buffer)
+                    if rate is not None:
+                        env.success_rate = rate
+                elif len(reach_goal_buffer) > 0:
                     env.success_rate = statistics.mean(reach_goal_buffer)
+            if logging:
                 self._log(it, losses, mean_hist_latent_loss, collection_time, learn_time, buffers, ep_infos)
                 if it % self.save_interval == 0:
                     self.save(os.path.join(self.log_dir, "model.pt"))
@@ -348,6 +357,14 @@ class OnPolicyRunner:
         self.current_learning_iteration = tot_iter
         if logging:
             self.save(os.path.join(self.log_dir, "model.pt"))
+
+    def _job_success_rate(self, window):
+        """mean of all ranks' reach-goal windows from one all-reduce of (sum, count), in float64: every rank gets the same number"""
+        on_gpu = torch.device(self.device).type == "cuda" and dist.get_backend() == "nccl"
+        t = torch.tensor([float(sum(window)), float(len(window))], dtype=torch.float64, device=self.device if on_gpu else "cpu")
+        dist.all_reduce(t)
+        s, c = t.tolist()
+        return s / c if c > 0 else None
 
     # ------------------------------------------------------------------ the vision student's env step: the part without autograd as recorded launches
     def _vision_env_step(self, vs, n_cmd):
@@ -561,6 +578,10 @@ class OnPolicyRunner:
             for tag, k in (("mean_reward", "rew"), ("mean_reward_i", "rew_i"), ("mean_reward_t", "rew_t"), ("mean_episode_length", "len")):
                 w.add_scalar("Train/" + tag, statistics.mean(buffers[k]), it)
             w.add_scalar("Train/success_rate", float(self.env.success_rate), it)
+        if getattr(self.env, "obstacle_curriculum_armed", False):
+            _count, bar, tyre, _gc = self.env._oc.read_state()      # one host read per logged iteration
+            w.add_scalar("Curr/bar_jump_bias", bar, it)
+            w.add_scalar("Curr/tire_jump_bias", tyre, it)
         if hasattr(w, "flush"):
             w.flush()
 
