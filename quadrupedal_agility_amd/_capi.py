@@ -6,6 +6,8 @@ __graft_entry__.build()).  It never falls back to a CPU path: a missing library 
 import ctypes as C
 import os
 
+import torch
+
 QA_ABI_VERSION = 18
 NUM_DOF = 12
 NUM_GAITS = 5
@@ -393,9 +395,8 @@ def load_library():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). quadrupedal_agility_amd has no CPU fallback.")
         # PyTorch ships its own HIP runtime (torch/lib/libamdhip64.so); the device pointers and streams this library is
-        # handed belong to THAT runtime.  Loading torch first makes our DT_NEEDED libamdhip64 resolve to the copy already in
-        # the process -- loaded the other way round, the process holds two runtimes and ours sees no device.
-        import torch  # noqa: F401
+        # handed belong to THAT runtime.  torch is imported at the top of this module, so our DT_NEEDED libamdhip64 resolves to
+        # the copy already in the process -- loaded the other way round, the process holds two runtimes and ours sees no device.
         lib = C.CDLL(LIB_PATH)
         bind(lib, "qa_")
         bind_extensions(lib, "qa_")
@@ -413,3 +414,78 @@ def tensor_info(lib, prefix, cfg, which):
     if rc != 0:
         raise RuntimeError(f"{prefix}tensor_info({which}) -> {rc}")
     return off.value, tuple(shape[i] for i in range(nd.value)), dt.value
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def stream(on):
+    """the CURRENT stream of a torch.device, or of a tensor's device, as the C ABI takes it; None on the CPU (the oracle's twins ignore it)"""
+    dev = on if type(on) is torch.device else on.device
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+
+
+NO_ERROR_TEXT = "(an injected library: no error text)"
+
+
+class Api:
+    """The one way to call an entry point of include/qa_sim.h from Python: `API.launch("slab_sum", ..., on=tensor)` appends the current stream
+    of `on`, `API.call("set_lean_exports", ...)` appends nothing; both raise RuntimeError on a non-zero status.  `lib` / `prefix` inject another
+    library exporting the same entry points under another prefix (the tests pass the oracle's twins); the default is libqa_sim.so, loaded at the
+    first use, and it is required.  Entry points that return a COUNT (`*_scratch_bytes`, `arena_bytes`, `mlp_strands`, ...) are called on
+    `fn(name)` / `lib` directly: they have no status to check."""
+
+    stream = staticmethod(stream)
+
+    def __init__(self, lib=None, prefix="qa_"):
+        self._lib, self.prefix = lib, prefix
+        self._fns = {}
+
+    @property
+    def lib(self):
+        if self._lib is None:
+            self._lib = load_library()
+        return self._lib
+
+    def fn(self, name):
+        f = self._fns.get(name)
+        if f is None:
+            f = self._fns[name] = getattr(self.lib, self.prefix + name)
+        return f
+
+    def check(self, name, rc):
+        """the status check itself, for a site that has to look at the code (or tidy up) before it raises"""
+        if rc != 0:
+            last = getattr(self.lib, self.prefix + "last_error", None)
+            text = last() if last is not None else NO_ERROR_TEXT
+            raise RuntimeError(f"{self.prefix}{name} failed with code {rc}: {text.decode() if isinstance(text, bytes) else text}")
+
+    def call(self, name, *args):
+        rc = self.fn(name)(*args)
+        if rc != 0:
+            self.check(name, rc)
+
+    def launch(self, name, *args, on):
+        rc = self.fn(name)(*args, stream(on))
+        if rc != 0:
+            self.check(name, rc)
+
+
+API = Api()
+
+_scratch = {}
+
+
+def scratch_for(dev, nbytes, floor=0):
+    """A scratch buffer of at least `nbytes` for a launch on the current stream of `dev`, kept per device AND stream (two launches on two
+    streams must not share partial sums) and per `floor` (the size a new buffer has at least: each caller keeps its own buffer and sizing)."""
+    if torch.cuda.is_current_stream_capturing():
+        # a recording bakes the address in: the buffer must belong to the graph's pool, never to a cache whose buffer a later, larger request
+        # replaces -- the old block would go back to the allocator and the replays would write partial sums into freed memory (ADVICE r3)
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream, floor)
+    buf = _scratch.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _scratch[key] = torch.empty(max(nbytes, floor), dtype=torch.uint8, device=dev)
+    return buf

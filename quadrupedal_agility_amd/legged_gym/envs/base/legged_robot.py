@@ -10,7 +10,6 @@ Nothing here computes physics, rewards or observations on the host: if the HIP l
 built the constructor raises.
 """
 import numpy as np
-import ctypes as C
 
 import torch
 
@@ -343,12 +342,9 @@ class LeggedRobot:
             # rollouts: the bin index follows the DEVICE step counter (a host parity baked into a recording is only right when
             # num_steps_per_env is even); the kernel accumulated into bin (step & 1) with step = counter - 1
             snap = torch.empty_like(self._episode_means)      # per-step values for the runner's per-iteration mean over the 24 steps
-            lib = _capi.load_library()
-            P = lambda t: C.c_void_p(t.data_ptr())
-            rc = lib.qa_episode_means(P(stats), P(self._step_ctr) if self._step_ctr is not None else None, int(self.common_step_counter), _capi.NUM_REWARDS,
-                                      float(self.max_episode_length_s), P(self._episode_means), P(snap), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"qa_episode_means failed with code {rc}: {lib.qa_last_error().decode()}")
+            P = _capi._ptr
+            _capi.API.launch("episode_means", P(stats), P(self._step_ctr) if self._step_ctr is not None else None, int(self.common_step_counter), _capi.NUM_REWARDS,
+                             float(self.max_episode_length_s), P(self._episode_means), P(snap), on=stats)
         else:
             if self._step_ctr is not None:
                 st = stats.index_select(0, (self._step_ctr - 1) & 1)[0]

@@ -8,13 +8,10 @@ import os
 import torch
 
 from quadrupedal_agility_amd import _capi
+from quadrupedal_agility_amd._capi import API, _ptr
 
 
 ENABLED = True      # tests flip this to compare against the unfused modules
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def _f32c(t):
@@ -28,23 +25,8 @@ class _PpoLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, std, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
                 clip, c_surr, c_value, c_bound, c_entropy, clipped_value):
-        lib = _capi.load_library()
-        mu_c, std_c, val_c = _f32c(mu), _f32c(std), _f32c(value)
-        fixed = [_f32c(x) for x in (actions, old_logp, old_mu, old_sigma, advantages, returns, target_values)]
-        B = mu_c.shape[0]
-        assert mu_c.is_cuda and mu_c.shape == (B, 12) and std_c.numel() == 12 and val_c.numel() == B
-        dmu = torch.empty_like(mu_c)
-        dstd = torch.empty(12, dtype=torch.float32, device=mu_c.device)
-        dvalue = torch.empty(B, dtype=torch.float32, device=mu_c.device)
-        out = torch.empty(8, dtype=torch.float32, device=mu_c.device)
-        nscratch = int(lib.qa_ppo_loss_scratch_bytes(B))
-        scratch = torch.empty(nscratch, dtype=torch.uint8, device=mu_c.device)
-        stream = C.c_void_p(torch.cuda.current_stream(mu_c.device).cuda_stream)
-        rc = lib.qa_ppo_loss(_ptr(mu_c), _ptr(std_c), _ptr(val_c), *[_ptr(x) for x in fixed], B, 12, float(clip), float(c_surr),
-                             float(c_value), float(c_bound), float(c_entropy), int(bool(clipped_value)),
-                             _ptr(dmu), _ptr(dstd), _ptr(dvalue), _ptr(out), _ptr(scratch), nscratch, stream)
-        if rc != 0:
-            raise RuntimeError(f"qa_ppo_loss failed with code {rc}: {lib.qa_last_error().decode()}")
+        out, dmu, dstd, dvalue = ppo_loss_raw(mu, std, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values, clip=clip, c_surr=c_surr,
+                                              c_value=c_value, c_bound=c_bound, c_entropy=c_entropy, clipped_value=clipped_value)
         ctx.save_for_backward(dmu, dstd, dvalue)
         ctx.value_shape = value.shape
         ctx.std_shape = std.shape
@@ -63,7 +45,6 @@ def ppo_loss_raw(mu, std, value, actions, old_logp, old_mu, old_sigma, advantage
     """qa_ppo_loss without the autograd wrapper: (stats[8], d loss/d mu (B,12), d loss/d std (12), d loss/d value (B)).  The
     caller feeds the gradients straight into autograd.backward() of the network outputs -- no scalar loss node, so none of
     the ones-fill / scale / accumulate launches a `loss.backward()` spends on it."""
-    lib = _capi.load_library()
     mu_c, std_c, val_c = _f32c(mu.detach()), _f32c(std.detach()), _f32c(value.detach())
     fixed = [_f32c(x) for x in (actions, old_logp, old_mu, old_sigma, advantages, returns, target_values)]
     B = mu_c.shape[0]
@@ -72,14 +53,11 @@ def ppo_loss_raw(mu, std, value, actions, old_logp, old_mu, old_sigma, advantage
     dstd = torch.empty(12, dtype=torch.float32, device=mu_c.device)
     dvalue = torch.empty(B, dtype=torch.float32, device=mu_c.device)
     out = torch.empty(8, dtype=torch.float32, device=mu_c.device)
-    nscratch = int(lib.qa_ppo_loss_scratch_bytes(B))
+    nscratch = int(API.lib.qa_ppo_loss_scratch_bytes(B))
     scratch = torch.empty(nscratch, dtype=torch.uint8, device=mu_c.device)
-    rc = lib.qa_ppo_loss(_ptr(mu_c), _ptr(std_c), _ptr(val_c), *[_ptr(x) for x in fixed], B, 12, float(clip), float(c_surr),
-                         float(c_value), float(c_bound), float(c_entropy), int(bool(clipped_value)),
-                         _ptr(dmu), _ptr(dstd), _ptr(dvalue), _ptr(out), _ptr(scratch), nscratch,
-                         C.c_void_p(torch.cuda.current_stream(mu_c.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"qa_ppo_loss failed with code {rc}: {lib.qa_last_error().decode()}")
+    API.launch("ppo_loss", _ptr(mu_c), _ptr(std_c), _ptr(val_c), *[_ptr(x) for x in fixed], B, 12, float(clip), float(c_surr),
+               float(c_value), float(c_bound), float(c_entropy), int(bool(clipped_value)),
+               _ptr(dmu), _ptr(dstd), _ptr(dvalue), _ptr(out), _ptr(scratch), nscratch, on=mu_c)
     return out, dmu, dstd, dvalue
 
 
@@ -87,7 +65,6 @@ def hybrid_ppo_loss_raw(logits, mean, std, value, actions, old_logp_d, old_logp_
                         clip, c_value, c_entropy, clipped_value=True):
     """qa_hybrid_ppo_loss (the task-level learner's categorical + Gaussian objective): (out[8], d loss/d logits (B,3), d mean (B,18),
     d std (18), d value (B)); None when the head widths are not the built ones (the caller keeps its eager expression)."""
-    lib = _capi.load_library()
     lg, mu_c, std_c, val_c = (_f32c(x.detach()) for x in (logits, mean, std, value))
     B, nd, nc = lg.shape[0], lg.shape[1], mu_c.shape[1]
     if (nd, nc) != (3, 18):
@@ -97,13 +74,10 @@ def hybrid_ppo_loss_raw(logits, mean, std, value, actions, old_logp_d, old_logp_
     dev = lg.device
     dlogits, dmean = torch.empty_like(lg), torch.empty_like(mu_c)
     dstd, dvalue, out = torch.empty(nc, device=dev), torch.empty(B, device=dev), torch.empty(8, device=dev)
-    n = int(lib.qa_hybrid_ppo_loss_scratch_bytes(B))
+    n = int(API.lib.qa_hybrid_ppo_loss_scratch_bytes(B))
     scratch = torch.empty(n, dtype=torch.uint8, device=dev)
-    rc = lib.qa_hybrid_ppo_loss(_ptr(lg), _ptr(mu_c), _ptr(std_c), _ptr(val_c), *[_ptr(x) for x in fixed], B, nd, nc, float(clip), float(c_value),
-                                float(c_entropy), int(bool(clipped_value)), _ptr(dlogits), _ptr(dmean), _ptr(dstd), _ptr(dvalue), _ptr(out),
-                                _ptr(scratch), n, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"qa_hybrid_ppo_loss failed with code {rc}: {lib.qa_last_error().decode()}")
+    API.launch("hybrid_ppo_loss", _ptr(lg), _ptr(mu_c), _ptr(std_c), _ptr(val_c), *[_ptr(x) for x in fixed], B, nd, nc, float(clip), float(c_value),
+               float(c_entropy), int(bool(clipped_value)), _ptr(dlogits), _ptr(dmean), _ptr(dstd), _ptr(dvalue), _ptr(out), _ptr(scratch), n, on=dev)
     return out, dlogits, dmean, dstd, dvalue
 
 
@@ -171,7 +145,6 @@ def _second_gradient(param):
     returned -- which is either still waiting in the engine's input buffer (same backward call: the engine adds after this node returns, and
     orders that after everything launched here) or has become `.grad` (an earlier backward call: autograd adopts the placeholder's
     storage, or cloned it, in which case `.grad` itself is the destination).  From here on the parameter gets finished gradients only."""
-    lib = _capi.load_library()
     p, parts, nparts, stride, alias, stream = _PENDING.pop(param.data_ptr())
     _NO_DEFER.add(param.data_ptr())
     dst = alias if (p.grad is None or p.grad.data_ptr() == alias.data_ptr()) else p.grad
@@ -180,8 +153,8 @@ def _second_gradient(param):
     cur = torch.cuda.current_stream(p.device)
     if stream is not None and stream != cur:
         cur.wait_stream(stream)          # the parts were written on the stream the first node ran on
-    _check(lib.qa_grad_reduce((C.c_void_p * 1)(dst.data_ptr()), (C.c_void_p * 1)(parts.data_ptr()), (C.c_int64 * 1)(stride), (C.c_int32 * 1)(nparts),
-                              (C.c_int32 * 1)(p.numel()), 1, C.c_void_p(cur.cuda_stream)), "qa_grad_reduce")
+    API.launch("grad_reduce", (C.c_void_p * 1)(dst.data_ptr()), (C.c_void_p * 1)(parts.data_ptr()), (C.c_int64 * 1)(stride), (C.c_int32 * 1)(nparts),
+               (C.c_int32 * 1)(p.numel()), 1, on=p)
     _retire(parts)
 
 
@@ -213,7 +186,6 @@ def flush_pending_grads(params=None):
     keys = list(_PENDING) if params is None else [p.data_ptr() for p in params if p.data_ptr() in _PENDING]
     if not keys:
         return
-    lib = _capi.load_library()
     ent = [_PENDING.pop(k) for k in keys]
     for p, *_ in ent:
         if p.grad is None or not p.grad.is_contiguous():
@@ -223,7 +195,7 @@ def flush_pending_grads(params=None):
         n = len(e)
         dst = (C.c_void_p * n)(*[x[0].grad.data_ptr() for x in e]); src = (C.c_void_p * n)(*[x[1].data_ptr() for x in e])
         stride = (C.c_int64 * n)(*[x[3] for x in e]); parts = (C.c_int32 * n)(*[x[2] for x in e]); numel = (C.c_int32 * n)(*[x[0].numel() for x in e])
-        _check(lib.qa_grad_reduce(dst, src, stride, parts, numel, n, C.c_void_p(torch.cuda.current_stream(e[0][0].device).cuda_stream)), "qa_grad_reduce")
+        API.launch("grad_reduce", dst, src, stride, parts, numel, n, on=e[0][0])
     for e in ent:
         _retire(e[1])
 
@@ -251,19 +223,15 @@ class _LinearElu(torch.autograd.Function):
     def backward(ctx, gy):
         x, weight, y = ctx.saved_tensors
         bias = ctx.bias_param
-        lib = _capi.load_library()
         _gradient_arriving(weight, bias)
         gy = _f32c(gy)
         rows, cols = y.shape
         g = torch.empty_like(y)
         gb = torch.empty(cols, dtype=torch.float32, device=y.device)
-        nscratch = int(lib.qa_elu_backward_bias_scratch_bytes(rows, cols))
+        nscratch = int(API.lib.qa_elu_backward_bias_scratch_bytes(rows, cols))
         scratch = torch.empty(nscratch, dtype=torch.uint8, device=y.device)
-        stream = C.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
         defer_b = ctx.needs_input_grad[2] and _defer_ok(bias) and bias.numel() == cols
-        rc = lib.qa_elu_backward_bias(_ptr(gy), _ptr(y), _ptr(g), None if defer_b else _ptr(gb), rows, cols, float(ctx.alpha), _ptr(scratch), nscratch, stream)
-        if rc != 0:
-            raise RuntimeError(f"qa_elu_backward_bias failed with code {rc}: {lib.qa_last_error().decode()}")
+        API.launch("elu_backward_bias", _ptr(gy), _ptr(y), _ptr(g), None if defer_b else _ptr(gb), rows, cols, float(ctx.alpha), _ptr(scratch), nscratch, on=y)
         if defer_b:           # the optimiser's first pass adds the (rows / 64) rows of column sums; autograd gets an unwritten placeholder
             gb = _register_parts(bias, scratch, (rows + 63) // 64, cols)
         gx = g.mm(weight) if ctx.needs_input_grad[0] else None
@@ -301,18 +269,7 @@ class _LinearRelu(torch.autograd.Function):
 
 def _masked_colsum(gy, y):
     """(gy * [y > 0], column sums of that): qa_elu_backward_bias with alpha = 0"""
-    lib = _capi.load_library()
-    gy, y = _f32c(gy), _f32c(y)
-    rows, cols = y.shape
-    g = torch.empty_like(y)
-    gb = torch.empty(cols, dtype=torch.float32, device=y.device)
-    nscratch = int(lib.qa_elu_backward_bias_scratch_bytes(rows, cols))
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=y.device)
-    rc = lib.qa_elu_backward_bias(_ptr(gy), _ptr(y), _ptr(g), _ptr(gb), rows, cols, 0.0, _ptr(scratch), nscratch,
-                                  C.c_void_p(torch.cuda.current_stream(y.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"qa_elu_backward_bias failed with code {rc}: {lib.qa_last_error().decode()}")
-    return g, gb
+    return _elu_bwd(gy, y, 0.0)
 
 
 def linear_relu(m, x):
@@ -382,18 +339,14 @@ class _NarrowLinear(torch.autograd.Function):
         gx = gy.mm(weight) if ctx.needs_input_grad[0] else None
         if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
             return gx, None, None
-        lib = _capi.load_library()
         xc = _f32c(x)
         rows, k = xc.shape
         o = weight.shape[0]
         gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
         gb = torch.empty(o, dtype=torch.float32, device=x.device)
-        n = int(lib.qa_narrow_wgrad_scratch_bytes(rows, o, k))
+        n = int(API.lib.qa_narrow_wgrad_scratch_bytes(rows, o, k))
         scratch = torch.empty(n, dtype=torch.uint8, device=x.device)
-        rc = lib.qa_narrow_wgrad(_ptr(gy), _ptr(xc), rows, o, k, _ptr(gw), _ptr(gb), _ptr(scratch), n,
-                                 C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"qa_narrow_wgrad failed with code {rc}: {lib.qa_last_error().decode()}")
+        API.launch("narrow_wgrad", _ptr(gy), _ptr(xc), rows, o, k, _ptr(gw), _ptr(gb), _ptr(scratch), n, on=x)
         return gx, gw, gb
 
 
@@ -499,11 +452,6 @@ def uniform_activation(*nets):
     return codes.pop() if len(codes) == 1 else None
 
 
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with code {rc}: {_capi.load_library().qa_last_error().decode()}")
-
-
 def _rows2d(t):
     """a (rows, cols) fp32 view whose rows are contiguous (a column slice of wider rows is fine: the kernels take a leading dimension)"""
     if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.data_ptr() % 4:
@@ -513,69 +461,49 @@ def _rows2d(t):
 
 def linear_forward_raw(x, weight, bias, act, alpha=1.0, out=None):
     """act(x W^T + b) by qa_linear_forward (one launch, bias and activation in the GEMM's epilogue)"""
-    lib = _capi.load_library()
     x = _rows2d(x)
     rows, k = x.shape
     n = weight.shape[0]
     y = out if out is not None else torch.empty(rows, n, dtype=torch.float32, device=x.device)
-    _check(lib.qa_linear_forward(_ptr(x), x.stride(0), _ptr(weight), weight.stride(0), _ptr(bias) if bias is not None else None, _ptr(y), y.stride(0),
-                                 rows, k, n, int(act), float(alpha), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "qa_linear_forward")
+    API.launch("linear_forward", _ptr(x), x.stride(0), _ptr(weight), weight.stride(0), _ptr(bias) if bias is not None else None, _ptr(y), y.stride(0),
+               rows, k, n, int(act), float(alpha), on=x)
     return y
-
-
-_split_scratch = {}
 
 
 def linear_forward_split_raw(x, weight, bias, act, alpha=1.0):
     """act(x W^T + b) by qa_linear_forward_split: the reduction dimension split over workgroups (few outputs, very long rows)"""
-    lib = _capi.load_library()
     x = _rows2d(x)
     rows, k = x.shape
     n = weight.shape[0]
-    nb = lib.qa_linear_forward_split_scratch_bytes(rows, k, n)
-    if torch.cuda.is_current_stream_capturing():
-        # a recording bakes the address in: allocate from the graph's pool (as linear_backward_weight_raw does), never from a cache whose
-        # buffer a later, larger request replaces -- the replays would write partial sums into freed memory (ADVICE r3)
-        sc = torch.empty(max(nb, 16), dtype=torch.uint8, device=x.device)
-    else:
-        key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
-        sc = _split_scratch.get(key)
-        if sc is None or sc.numel() < nb:
-            sc = torch.empty(nb, dtype=torch.uint8, device=x.device)
-            _split_scratch[key] = sc
+    sc = _capi.scratch_for(x.device, API.lib.qa_linear_forward_split_scratch_bytes(rows, k, n))
     y = torch.empty(rows, n, dtype=torch.float32, device=x.device)
-    _check(lib.qa_linear_forward_split(_ptr(x), x.stride(0), _ptr(weight), weight.stride(0), _ptr(bias) if bias is not None else None, _ptr(y), n, rows, k, n,
-                                       int(act), float(alpha), _ptr(sc), sc.numel(), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
-           "qa_linear_forward_split")
+    API.launch("linear_forward_split", _ptr(x), x.stride(0), _ptr(weight), weight.stride(0), _ptr(bias) if bias is not None else None, _ptr(y), n, rows, k, n,
+               int(act), float(alpha), _ptr(sc), sc.numel(), on=x)
     return y
 
 
 def linear_backward_input_raw(g, weight, y_prev, act_prev, alpha=1.0):
     """(g W) * act'(y_prev) by qa_linear_backward_input: the input gradient of a layer with the previous layer's activation derivative"""
-    lib = _capi.load_library()
     g = _rows2d(g)
     rows, n = g.shape
     k = weight.shape[1]
     gin = torch.empty(rows, k, dtype=torch.float32, device=g.device)
     yp = _rows2d(y_prev) if (act_prev and y_prev is not None) else None
-    _check(lib.qa_linear_backward_input(_ptr(g), g.stride(0), _ptr(weight), weight.stride(0), _ptr(yp) if yp is not None else None,
-                                        yp.stride(0) if yp is not None else 0, _ptr(gin), k, rows, k, n, int(act_prev if yp is not None else 0), float(alpha),
-                                        C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)), "qa_linear_backward_input")
+    API.launch("linear_backward_input", _ptr(g), g.stride(0), _ptr(weight), weight.stride(0), _ptr(yp) if yp is not None else None,
+               yp.stride(0) if yp is not None else 0, _ptr(gin), k, rows, k, n, int(act_prev if yp is not None else 0), float(alpha), on=g)
     return gin
 
 
 def linear_backward_weight_raw(g, x, want_bias=True):
     """(g^T x, column sums of g) by qa_linear_backward_weight (split over row slabs, fixed-order reduction)"""
-    lib = _capi.load_library()
     g, x = _rows2d(g), _rows2d(x)
     rows, n = g.shape
     k = x.shape[1]
     gw = torch.empty(n, k, dtype=torch.float32, device=g.device)
     gb = torch.empty(n, dtype=torch.float32, device=g.device)
-    nb = int(lib.qa_linear_backward_weight_scratch_bytes(rows, k, n))
+    nb = int(API.lib.qa_linear_backward_weight_scratch_bytes(rows, k, n))
     scratch = torch.empty(nb, dtype=torch.uint8, device=g.device)
-    _check(lib.qa_linear_backward_weight(_ptr(g), g.stride(0), _ptr(x), x.stride(0), _ptr(gw), _ptr(gb), rows, k, n, _ptr(scratch), nb,
-                                         C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)), "qa_linear_backward_weight")
+    API.launch("linear_backward_weight", _ptr(g), g.stride(0), _ptr(x), x.stride(0), _ptr(gw), _ptr(gb), rows, k, n, _ptr(scratch), nb, on=g)
     return gw, gb
 
 
@@ -609,11 +537,10 @@ def pad_k():
 
 def slab_sum(parts):
     """sum over the leading dimension of a contiguous (S, ...) tensor by qa_slab_sum (fixed order) -- not torch's sum(0)"""
-    lib = _capi.load_library()
     S = parts.shape[0]
     out = torch.empty(parts.shape[1:], dtype=torch.float32, device=parts.device)
     n = out.numel()
-    _check(lib.qa_slab_sum(_ptr(parts), n, S, n, _ptr(out), C.c_void_p(torch.cuda.current_stream(parts.device).cuda_stream)), "qa_slab_sum")
+    API.launch("slab_sum", _ptr(parts), n, S, n, _ptr(out), on=parts)
     return out
 
 
@@ -671,15 +598,14 @@ class _MlpChain(torch.autograd.Function):
 
 
 def _elu_bwd(gy, y, alpha):
-    lib = _capi.load_library()
+    """(gy * elu'(y), column sums of that) by qa_elu_backward_bias; alpha = 0 IS ReLU's mask"""
     gy, y = _f32c(gy), _f32c(y)
     rows, cols = y.shape
     g = torch.empty_like(y)
     gb = torch.empty(cols, dtype=torch.float32, device=y.device)
-    nscratch = int(lib.qa_elu_backward_bias_scratch_bytes(rows, cols))
+    nscratch = int(API.lib.qa_elu_backward_bias_scratch_bytes(rows, cols))
     scratch = torch.empty(nscratch, dtype=torch.uint8, device=y.device)
-    _check(lib.qa_elu_backward_bias(_ptr(gy), _ptr(y), _ptr(g), _ptr(gb), rows, cols, float(alpha), _ptr(scratch), nscratch,
-                                    C.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)), "qa_elu_backward_bias")
+    API.launch("elu_backward_bias", _ptr(gy), _ptr(y), _ptr(g), _ptr(gb), rows, cols, float(alpha), _ptr(scratch), nscratch, on=y)
     return g, gb
 
 
@@ -873,28 +799,20 @@ def ppo_loss_reference(mu, std, value, actions, old_logp, old_mu, old_sigma, adv
 
 def normalizer_update(mean, var, count, batches):
     """RunningMeanStd update of the device-resident double moments with 1..4 fp32 batches, one launch (qa_normalizer_update)."""
-    lib = _capi.load_library()
     bs = [_f32c(b.detach()) for b in batches]
     k, d = len(bs), mean.shape[0]
     assert 1 <= k <= 4 and all(b.dim() == 2 and b.shape[1] == d for b in bs) and mean.dtype == torch.float64
     ptrs = (C.c_void_p * k)(*[b.data_ptr() for b in bs])
     rows = (C.c_int64 * k)(*[b.shape[0] for b in bs])
-    stream = C.c_void_p(torch.cuda.current_stream(mean.device).cuda_stream)
-    rc = lib.qa_normalizer_update(ptrs, rows, k, d, _ptr(mean), _ptr(var), _ptr(count), stream)
-    if rc != 0:
-        raise RuntimeError(f"qa_normalizer_update failed with code {rc}: {lib.qa_last_error().decode()}")
+    API.launch("normalizer_update", ptrs, rows, k, d, _ptr(mean), _ptr(var), _ptr(count), on=mean)
 
 
 def normalizer_apply(x, mean, var, epsilon, clip):
-    lib = _capi.load_library()
     xc = _f32c(x)
     y = torch.empty_like(xc)
     d = mean.shape[0]
     assert xc.shape[-1] == d
-    stream = C.c_void_p(torch.cuda.current_stream(xc.device).cuda_stream)
-    rc = lib.qa_normalizer_apply(_ptr(xc), _ptr(y), xc.numel() // d, d, _ptr(mean), _ptr(var), float(epsilon), float(clip), stream)
-    if rc != 0:
-        raise RuntimeError(f"qa_normalizer_apply failed with code {rc}: {lib.qa_last_error().decode()}")
+    API.launch("normalizer_apply", _ptr(xc), _ptr(y), xc.numel() // d, d, _ptr(mean), _ptr(var), float(epsilon), float(clip), on=xc)
     return y
 
 
@@ -907,18 +825,7 @@ class _PairLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b, mode):
-        a = _f32c(a)
-        assert b.dtype == torch.float32 and b.stride(1) == 1 and a.shape == b.shape
-        rows, cols = a.shape
-        lib = _capi.load_library()
-        grad = torch.empty_like(a)
-        out = torch.empty((), dtype=torch.float32, device=a.device)
-        nscratch = int(lib.qa_pair_loss_scratch_bytes(rows))
-        scratch = torch.empty(nscratch, dtype=torch.uint8, device=a.device)
-        rc = lib.qa_pair_loss(_ptr(a), _ptr(b), rows, cols, b.stride(0), int(mode), _ptr(grad), _ptr(out), _ptr(scratch), nscratch,
-                              C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"qa_pair_loss failed with code {rc}: {lib.qa_last_error().decode()}")
+        out, grad = pair_loss_raw(a, b, mode)
         ctx.save_for_backward(grad)
         return out
 
@@ -937,15 +844,11 @@ def pair_loss_raw(a, b, mode):
     a = _f32c(a.detach())
     assert b.dtype == torch.float32 and b.stride(1) == 1 and a.shape == b.shape
     rows, cols = a.shape
-    lib = _capi.load_library()
     grad = torch.empty_like(a)
     out = torch.empty((), dtype=torch.float32, device=a.device)
-    nscratch = int(lib.qa_pair_loss_scratch_bytes(rows))
+    nscratch = int(API.lib.qa_pair_loss_scratch_bytes(rows))
     scratch = torch.empty(nscratch, dtype=torch.uint8, device=a.device)
-    rc = lib.qa_pair_loss(_ptr(a), _ptr(b), rows, cols, b.stride(0), int(mode), _ptr(grad), _ptr(out), _ptr(scratch), nscratch,
-                          C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"qa_pair_loss failed with code {rc}: {lib.qa_last_error().decode()}")
+    API.launch("pair_loss", _ptr(a), _ptr(b), rows, cols, b.stride(0), int(mode), _ptr(grad), _ptr(out), _ptr(scratch), nscratch, on=a)
     return out, grad
 
 
@@ -956,7 +859,6 @@ def pair_losses_raw(jobs):
     """several qa_pair_loss problems in ONE launch (qa_pair_losses, ABI 18).  jobs: [(a, b, mode, grad_scale)] with grad_scale a 0-d ROCm tensor or None;
     -> [(loss (0-d, unscaled), d loss / d a times grad_scale)].  The launches of one call site must follow each other on one stream (they share the
     arrival counter's word)."""
-    lib = _capi.load_library()
     n = len(jobs)
     recs = (_capi.QaPairJob * n)()
     outs, keep = [], []
@@ -972,12 +874,12 @@ def pair_losses_raw(jobs):
         r.a, r.b, r.rows, r.cols, r.mode, r.b_stride = a.data_ptr(), b.data_ptr(), a.shape[0], a.shape[1], int(mode), b.stride(0)
         r.grad_scale, r.grad_a, r.out = (scale.data_ptr() if scale is not None else None), grad.data_ptr(), out.data_ptr()
         outs.append((out, grad)); keep.append(a)
-    nb = int(lib.qa_pair_losses_scratch_bytes(C.cast(recs, C.c_void_p), n))
+    nb = int(API.lib.qa_pair_losses_scratch_bytes(C.cast(recs, C.c_void_p), n))
     key = (dev, nb)
     sc = _pair_scratch.get(key)
     if sc is None:
         sc = _pair_scratch[key] = torch.zeros(nb, dtype=torch.uint8, device=dev)          # the arrival counter: zeroed ONCE
-    _check(lib.qa_pair_losses(C.cast(recs, C.c_void_p), n, _ptr(sc), nb, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "qa_pair_losses")
+    API.launch("pair_losses", C.cast(recs, C.c_void_p), n, _ptr(sc), nb, on=dev)
     return outs
 
 
@@ -989,9 +891,7 @@ def accumulate_scalars(acc, scalars):
             and all(torch.is_tensor(x) and x.dtype == torch.float32 and x.numel() == 1 and x.device == acc.device for x in scalars)):
         acc[:n].add_(torch.stack([x.reshape(()) for x in scalars]))
         return
-    lib = _capi.load_library()
-    _check(lib.qa_accumulate_scalars(_ptr(acc), (C.c_void_p * n)(*[x.data_ptr() for x in scalars]), n, C.c_void_p(torch.cuda.current_stream(acc.device).cuda_stream)),
-           "qa_accumulate_scalars")
+    API.launch("accumulate_scalars", _ptr(acc), (C.c_void_p * n)(*[x.data_ptr() for x in scalars]), n, on=acc)
 
 
 def gather_rows(idx, srcs, dsts=None, block_dev=None):
@@ -1004,25 +904,25 @@ def gather_rows(idx, srcs, dsts=None, block_dev=None):
     assert idx.dtype == torch.int64 and idx.is_contiguous() and all(x.dtype == torch.float32 and x.stride(1) == 1 for x in flat)
     if dsts is None:
         dsts = [torch.empty(rows, x.shape[1], dtype=torch.float32, device=idx.device) for x in flat]
-    lib = _capi.load_library()
     src = (C.c_void_p * n)(*[x.data_ptr() for x in flat])
     dst = (C.c_void_p * n)(*[d.data_ptr() for d in dsts])
     strides = (C.c_int64 * n)(*[x.stride(0) for x in flat])
     widths = (C.c_int32 * n)(*[x.shape[1] for x in flat])
-    rc = lib.qa_gather_rows(_ptr(idx), _ptr(block_dev) if block_dev is not None else None, rows, n, src, strides, widths, dst,
-                            C.c_void_p(torch.cuda.current_stream(idx.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"qa_gather_rows failed with code {rc}: {lib.qa_last_error().decode()}")
+    API.launch("gather_rows", _ptr(idx), _ptr(block_dev) if block_dev is not None else None, rows, n, src, strides, widths, dst, on=idx)
     return dsts
 
 
 def kl_lr_rule(kl, desired_kl, lr, factor=1.5, lr_min=1e-5, lr_max=1e-2):
     """lr (0-d ROCm tensor) <- the KL-adaptive rule of gail.py:367-379 applied to kl (0-d ROCm tensor); one launch"""
-    lib = _capi.load_library()
-    rc = lib.qa_kl_lr_rule(_ptr(kl), float(desired_kl), float(factor), float(lr_min), float(lr_max), _ptr(lr),
-                           C.c_void_p(torch.cuda.current_stream(lr.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"qa_kl_lr_rule failed with code {rc}: {lib.qa_last_error().decode()}")
+    API.launch("kl_lr_rule", _ptr(kl), float(desired_kl), float(factor), float(lr_min), float(lr_max), _ptr(lr), on=lr)
+
+
+def _take_pending(params):
+    """the gradients of `params` that were in parts have been handed to an optimiser launch"""
+    for p in params:
+        e = _PENDING.pop(p.data_ptr(), None)
+        if e is not None:
+            _retire(e[1])
 
 
 class ClipAdam:
@@ -1141,31 +1041,24 @@ class ClipAdam:
             t["copied"] = torch.cuda.Event()
             t["copied"].record()
             t["grad_ptrs"] = ptrs
-        lib = _capi.load_library()
-        stream = C.c_void_p(torch.cuda.current_stream(params[0].device).cuda_stream)
         if pend is not None:
             n = len(params)
             src = (C.c_void_p * n)(*[(e[1].data_ptr() if e is not None else 0) for e in pend])
             stride = (C.c_int64 * n)(*[(e[3] if e is not None else 0) for e in pend])
             parts = (C.c_int32 * n)(*[(e[2] if e is not None else 0) for e in pend])
-            rc = lib.qa_clip_adam_step_reduce(_ptr(t["params"]), (C.c_void_p * n)(*ptrs), _ptr(t["exp_avg"]), _ptr(t["exp_avg_sq"]), _ptr(t["steps"]), t["n"],
-                                              _ptr(t["chunk_tensor"]), _ptr(t["chunk_start"]), _ptr(t["chunk_len"]), t["num_chunks"], _ptr(t["wd"]),
-                                              _ptr(lr_dev), float(t["betas"][0]), float(t["betas"][1]), float(t["eps"]), self.max_norm,
-                                              _ptr(t["scratch"]), t["scratch"].numel(), src, stride, parts, stream)
-            for p in params:
-                e = _PENDING.pop(p.data_ptr(), None)
-                if e is not None:
-                    _retire(e[1])
-            if rc != 0:
-                raise RuntimeError(f"qa_clip_adam_step_reduce failed with code {rc}: {lib.qa_last_error().decode()}")
+            try:
+                API.launch("clip_adam_step_reduce", _ptr(t["params"]), (C.c_void_p * n)(*ptrs), _ptr(t["exp_avg"]), _ptr(t["exp_avg_sq"]), _ptr(t["steps"]), t["n"],
+                           _ptr(t["chunk_tensor"]), _ptr(t["chunk_start"]), _ptr(t["chunk_len"]), t["num_chunks"], _ptr(t["wd"]),
+                           _ptr(lr_dev), float(t["betas"][0]), float(t["betas"][1]), float(t["eps"]), self.max_norm,
+                           _ptr(t["scratch"]), t["scratch"].numel(), src, stride, parts, on=params[0])
+            finally:          # taken or refused, the parts are not pending any more
+                _take_pending(params)
             return
-        fn, garg = (lib.qa_clip_adam_step_hostgrads, (C.c_void_p * len(ptrs))(*ptrs)) if inline else (lib.qa_clip_adam_step, _ptr(t["grads"]))
-        rc = fn(_ptr(t["params"]), garg, _ptr(t["exp_avg"]), _ptr(t["exp_avg_sq"]), _ptr(t["steps"]), t["n"],
-                                   _ptr(t["chunk_tensor"]), _ptr(t["chunk_start"]), _ptr(t["chunk_len"]), t["num_chunks"], _ptr(t["wd"]),
-                                   _ptr(lr_dev), float(t["betas"][0]), float(t["betas"][1]), float(t["eps"]), self.max_norm,
-                                   _ptr(t["scratch"]), t["scratch"].numel(), stream)
-        if rc != 0:
-            raise RuntimeError(f"qa_clip_adam_step failed with code {rc}: {lib.qa_last_error().decode()}")
+        name, garg = ("clip_adam_step_hostgrads", (C.c_void_p * len(ptrs))(*ptrs)) if inline else ("clip_adam_step", _ptr(t["grads"]))
+        API.launch(name, _ptr(t["params"]), garg, _ptr(t["exp_avg"]), _ptr(t["exp_avg_sq"]), _ptr(t["steps"]), t["n"],
+                   _ptr(t["chunk_tensor"]), _ptr(t["chunk_start"]), _ptr(t["chunk_len"]), t["num_chunks"], _ptr(t["wd"]),
+                   _ptr(lr_dev), float(t["betas"][0]), float(t["betas"][1]), float(t["eps"]), self.max_norm,
+                   _ptr(t["scratch"]), t["scratch"].numel(), on=params[0])
 
 
 class ClipAdamPair:
@@ -1227,19 +1120,14 @@ class ClipAdamPair:
         parts = (C.c_int32 * n)(*[(e[2] if e is not None else 0) for e in pend])
         pair = _capi.QaAdamPair(ta["n"], ta["num_chunks"], pb["lr_dev"].data_ptr(), b.max_norm, kl.data_ptr() if kl is not None else None,
                                 float(desired_kl) if kl is not None else 0.0, float(factor), float(lr_min), float(lr_max))
-        lib = _capi.load_library()
         params = pa["params"] + pb["params"]
-        rc = lib.qa_clip_adam_pair_step(_ptr(m["params"]), (C.c_void_p * n)(*ptrs), _ptr(m["exp_avg"]), _ptr(m["exp_avg_sq"]), _ptr(m["steps"]), m["n"],
-                                        _ptr(m["chunk_tensor"]), _ptr(m["chunk_start"]), _ptr(m["chunk_len"]), m["num_chunks"], _ptr(m["wd"]),
-                                        _ptr(pa["lr_dev"]), float(ta["betas"][0]), float(ta["betas"][1]), float(ta["eps"]), a.max_norm,
-                                        _ptr(m["scratch"]), m["scratch"].numel(), src, stride, parts, C.byref(pair),
-                                        C.c_void_p(torch.cuda.current_stream(params[0].device).cuda_stream))
-        for p in params:
-            e = _PENDING.pop(p.data_ptr(), None)
-            if e is not None:
-                _retire(e[1])
-        if rc != 0:
-            raise RuntimeError(f"qa_clip_adam_pair_step failed with code {rc}: {lib.qa_last_error().decode()}")
+        try:
+            API.launch("clip_adam_pair_step", _ptr(m["params"]), (C.c_void_p * n)(*ptrs), _ptr(m["exp_avg"]), _ptr(m["exp_avg_sq"]), _ptr(m["steps"]), m["n"],
+                       _ptr(m["chunk_tensor"]), _ptr(m["chunk_start"]), _ptr(m["chunk_len"]), m["num_chunks"], _ptr(m["wd"]),
+                       _ptr(pa["lr_dev"]), float(ta["betas"][0]), float(ta["betas"][1]), float(ta["eps"]), a.max_norm,
+                       _ptr(m["scratch"]), m["scratch"].numel(), src, stride, parts, C.byref(pair), on=params[0])
+        finally:
+            _take_pending(params)
         return True
 
 
@@ -1252,7 +1140,7 @@ class StackedAdam:
 
     def __init__(self, optimizers, lib=None, prefix="qa_"):
         self.opts = list(optimizers)
-        self._lib, self._prefix = lib, prefix
+        self.api = _capi.Api(lib, prefix)
         self._lr = {}
         self._ticket = None
         self._keep = None
@@ -1331,11 +1219,7 @@ class StackedAdam:
             p.grad = g
         self._keep = keep
         g0 = self.opts[0].param_groups[0]
-        lib = self._lib or _capi.load_library()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
-        rc = getattr(lib, self._prefix + "adam_stack_step")(C.cast(recs, C.c_void_p), n, float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), _ptr(self._ticket), stream)
-        if rc != 0:
-            raise RuntimeError(f"adam_stack_step failed with code {rc}" + (f": {lib.qa_last_error().decode()}" if self._prefix == "qa_" else ""))
+        self.api.launch("adam_stack_step", C.cast(recs, C.c_void_p), n, float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), _ptr(self._ticket), on=dev)
 
 
 class _DiscLoss(torch.autograd.Function):
@@ -1345,22 +1229,8 @@ class _DiscLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, d, eps, c, label_lb, policy_eps, policy_c, b_lb, b_pi, b_ulb, c_ss, info_coef_dev, c_disc, c_us):
-        lib = _capi.load_library()
-        dc, ec, cc = _f32c(d), _f32c(eps), _f32c(c)
-        pe, pc = _f32c(policy_eps), _f32c(policy_c)
-        lab = label_lb if (label_lb.dtype == torch.int64 and label_lb.is_contiguous()) else label_lb.contiguous().long()
-        B = b_lb + b_pi + b_ulb
-        assert dc.numel() == B and ec.numel() == B and cc.shape == (B, 5) and lab.numel() == b_lb and pe.numel() == b_pi and pc.shape == (b_pi, 5)
         assert info_coef_dev.is_cuda and info_coef_dev.dtype == torch.float32
-        gd = torch.empty(B, dtype=torch.float32, device=dc.device); ge = torch.empty_like(gd); gc = torch.empty_like(cc)
-        out = torch.empty(16, dtype=torch.float32, device=dc.device)
-        n = int(lib.qa_disc_loss_scratch_bytes(B))
-        scratch = torch.empty(n, dtype=torch.uint8, device=dc.device)
-        stream = C.c_void_p(torch.cuda.current_stream(dc.device).cuda_stream)
-        rc = lib.qa_disc_loss(_ptr(dc), _ptr(ec), _ptr(cc), _ptr(lab), _ptr(pe), _ptr(pc), b_lb, b_pi, b_ulb, float(c_ss), _ptr(info_coef_dev),
-                              float(c_disc), float(c_us), _ptr(gd), _ptr(ge), _ptr(gc), _ptr(out), _ptr(scratch), n, stream)
-        if rc != 0:
-            raise RuntimeError(f"qa_disc_loss failed with code {rc}: {lib.qa_last_error().decode()}")
+        out, gd, ge, gc = disc_loss_raw(d, eps, c, label_lb, policy_eps, policy_c, b_lb, b_pi, b_ulb, c_ss=c_ss, info_coef_dev=info_coef_dev, c_disc=c_disc, c_us=c_us)
         ctx.save_for_backward(gd, ge, gc)
         ctx.shapes = (d.shape, eps.shape, c.shape)
         ctx.mark_non_differentiable(out)
@@ -1376,7 +1246,6 @@ class _DiscLoss(torch.autograd.Function):
 def disc_loss_raw(d, eps, c, label_lb, policy_eps, policy_c, b_lb, b_pi, b_ulb, *, c_ss, info_coef_dev, c_disc, c_us, from_logits=False):
     """qa_disc_loss without the autograd wrapper: (stats[16], d loss/d d, d loss/d eps, d loss/d c) shaped like d, eps, c.  from_logits (qa_disc_loss_logits,
     ABI 18): `c` holds the class LOGITS -- the softmax and its backward run inside the launch, the last result is d loss / d logits"""
-    lib = _capi.load_library()
     dc, ec, cc = _f32c(d.detach()), _f32c(eps.detach()), _f32c(c.detach())
     pe, pc = _f32c(policy_eps), _f32c(policy_c)
     lab = label_lb if (label_lb.dtype == torch.int64 and label_lb.is_contiguous()) else label_lb.contiguous().long()
@@ -1384,14 +1253,10 @@ def disc_loss_raw(d, eps, c, label_lb, policy_eps, policy_c, b_lb, b_pi, b_ulb, 
     assert dc.numel() == B and ec.numel() == B and cc.shape == (B, 5) and lab.numel() == b_lb and pe.numel() == b_pi and pc.shape == (b_pi, 5)
     gd = torch.empty(B, dtype=torch.float32, device=dc.device); ge = torch.empty_like(gd); gc = torch.empty_like(cc)
     out = torch.empty(16, dtype=torch.float32, device=dc.device)
-    n = int(lib.qa_disc_loss_scratch_bytes(B))
+    n = int(API.lib.qa_disc_loss_scratch_bytes(B))
     scratch = torch.empty(n, dtype=torch.uint8, device=dc.device)
-    fn = lib.qa_disc_loss_logits if from_logits else lib.qa_disc_loss
-    rc = fn(_ptr(dc), _ptr(ec), _ptr(cc), _ptr(lab), _ptr(pe), _ptr(pc), b_lb, b_pi, b_ulb, float(c_ss), _ptr(info_coef_dev),
-            float(c_disc), float(c_us), _ptr(gd), _ptr(ge), _ptr(gc), _ptr(out), _ptr(scratch), n,
-            C.c_void_p(torch.cuda.current_stream(dc.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"qa_disc_loss failed with code {rc}: {lib.qa_last_error().decode()}")
+    API.launch("disc_loss_logits" if from_logits else "disc_loss", _ptr(dc), _ptr(ec), _ptr(cc), _ptr(lab), _ptr(pe), _ptr(pc), b_lb, b_pi, b_ulb, float(c_ss),
+               _ptr(info_coef_dev), float(c_disc), float(c_us), _ptr(gd), _ptr(ge), _ptr(gc), _ptr(out), _ptr(scratch), n, on=dc)
     return out, gd.view(d.shape), ge.view(eps.shape), gc.view(c.shape)
 
 
@@ -1399,7 +1264,6 @@ def disc_sample_prepare(tables, block_dev, srcs, eps_src, c_src, label_table, ta
     """minibatch `block_dev` of the update's index tables, read from (labelled expert, policy ring, unlabelled expert) straight into the
     prepared (3 mb, dim) matrix + the policy rows' (eps, c) + the labelled rows' classes: qa_disc_sample_prepare, one launch.
     `tables` = (t_lb, t_pi, t_ulb) int64 (steps, mb); returns (x_all, eps, c, label)."""
-    lib = _capi.load_library()
     dev = srcs[0].device
     mb = [t.shape[1] for t in tables]
     d = srcs[0].shape[1]
@@ -1416,9 +1280,8 @@ def disc_sample_prepare(tables, block_dev, srcs, eps_src, c_src, label_table, ta
     io.label_src, io.label_out, io.block_dev = label_table.data_ptr(), label.data_ptr(), block_dev.data_ptr()
     mean = _ptr(normalizer.mean) if normalizer is not None else None
     var = _ptr(normalizer.var) if normalizer is not None else None
-    _check(lib.qa_disc_sample_prepare(C.byref(io), d, cd, _ptr(task_mask), _ptr(frame_mult), _ptr(task_weight_dev) if task_weight_dev is not None else None, mean, var,
-                                      float(normalizer.epsilon) if normalizer is not None else 0.0, float(normalizer.clip_obs) if normalizer is not None else 0.0,
-                                      _ptr(x_all), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "qa_disc_sample_prepare")
+    API.launch("disc_sample_prepare", C.byref(io), d, cd, _ptr(task_mask), _ptr(frame_mult), _ptr(task_weight_dev) if task_weight_dev is not None else None, mean, var,
+               float(normalizer.epsilon) if normalizer is not None else 0.0, float(normalizer.clip_obs) if normalizer is not None else 0.0, _ptr(x_all), on=dev)
     return x_all, eps, c, label
 
 
@@ -1428,11 +1291,10 @@ _tail_scratch = {}
 def disc_step_tail(head_stats, input_grad, weights, acc=None, step=None, prior=None, prior_soft_coef=0.0):
     """the 11 logged values of a discriminator step by qa_disc_step_tail (sums of squares of the penalty's input gradient and of the
     regularised weights + the head statistics), optionally added to `acc`, `step` bumped and the class prior's EMA stepped, in ONE launch"""
-    lib = _capi.load_library()
     dev = head_stats.device
     sc = _tail_scratch.get(dev)
     if sc is None:
-        sc = torch.zeros(int(lib.qa_disc_step_tail_scratch_bytes()), dtype=torch.uint8, device=dev)      # holds the arrival counter: zeroed ONCE
+        sc = torch.zeros(int(API.lib.qa_disc_step_tail_scratch_bytes()), dtype=torch.uint8, device=dev)      # holds the arrival counter: zeroed ONCE
         _tail_scratch[dev] = sc
     g = _f32c(input_grad)
     ws = [w.detach() for w in weights]
@@ -1440,10 +1302,9 @@ def disc_step_tail(head_stats, input_grad, weights, acc=None, step=None, prior=N
     wp = (C.c_void_p * len(ws))(*[w.data_ptr() for w in ws])
     wn = (C.c_int64 * len(ws))(*[w.numel() for w in ws])
     out = torch.empty(11, dtype=torch.float32, device=dev)
-    _check(lib.qa_disc_step_tail(_ptr(head_stats), _ptr(g), g.shape[0], g.numel() // g.shape[0], wp, wn, len(ws), _ptr(out), _ptr(acc) if acc is not None else None,
-                                 _ptr(step) if step is not None else None, _ptr(prior) if prior is not None else None, prior.numel() if prior is not None else 0,
-                                 float(prior_soft_coef), _ptr(sc), sc.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-           "qa_disc_step_tail")
+    API.launch("disc_step_tail", _ptr(head_stats), _ptr(g), g.shape[0], g.numel() // g.shape[0], wp, wn, len(ws), _ptr(out), _ptr(acc) if acc is not None else None,
+               _ptr(step) if step is not None else None, _ptr(prior) if prior is not None else None, prior.numel() if prior is not None else 0,
+               float(prior_soft_coef), _ptr(sc), sc.numel(), on=dev)
     return out
 
 
@@ -1473,21 +1334,17 @@ def disc_loss_reference(d, eps, c, label_lb, policy_eps, policy_c, b_lb, b_pi, b
 def disc_prepare(batches, task_mask, frame_mult, task_weight_dev, normalizer=None):
     """[x_0; x_1; x_2] -> one (sum rows, dim) matrix with the discriminator's task weighting, frame weighting and (optionally)
     the running-moment normalisation + clip applied: one launch (qa_disc_prepare)."""
-    lib = _capi.load_library()
     bs = [_f32c(b.detach()) for b in batches]
     k, d = len(bs), bs[0].shape[1]
     assert 1 <= k <= 3 and all(b.dim() == 2 and b.shape[1] == d for b in bs)
     ptrs = (C.c_void_p * k)(*[b.data_ptr() for b in bs])
     rows = (C.c_int64 * k)(*[b.shape[0] for b in bs])
     out = torch.empty(sum(b.shape[0] for b in bs), d, dtype=torch.float32, device=bs[0].device)
-    stream = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
     mean = _ptr(normalizer.mean) if normalizer is not None else None
     var = _ptr(normalizer.var) if normalizer is not None else None
-    rc = lib.qa_disc_prepare(ptrs, rows, k, d, _ptr(task_mask), _ptr(frame_mult), _ptr(task_weight_dev) if task_weight_dev is not None else None,
-                             mean, var, float(normalizer.epsilon) if normalizer is not None else 0.0,
-                             float(normalizer.clip_obs) if normalizer is not None else 0.0, _ptr(out), stream)
-    if rc != 0:
-        raise RuntimeError(f"qa_disc_prepare failed with code {rc}: {lib.qa_last_error().decode()}")
+    API.launch("disc_prepare", ptrs, rows, k, d, _ptr(task_mask), _ptr(frame_mult), _ptr(task_weight_dev) if task_weight_dev is not None else None,
+               mean, var, float(normalizer.epsilon) if normalizer is not None else 0.0,
+               float(normalizer.clip_obs) if normalizer is not None else 0.0, _ptr(out), on=out)
     return out
 
 
@@ -1503,11 +1360,8 @@ def gae(rewards, values, dones, last_values, returns, advantages, gamma, lam, no
     scratch = _GAE_SCRATCH.get(rewards.device)
     if scratch is None:
         scratch = _GAE_SCRATCH[rewards.device] = torch.zeros(1024, dtype=torch.float32, device=rewards.device)
-    lib = _capi.load_library()
-    rc = lib.qa_gae(_ptr(rewards), _ptr(values), _ptr(dones), _ptr(last_values), _ptr(returns), _ptr(advantages), T, N, float(gamma),
-                    float(lam), int(bool(normalize)), _ptr(scratch), C.c_void_p(torch.cuda.current_stream(rewards.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"qa_gae failed with code {rc}: {lib.qa_last_error().decode()}")
+    API.launch("gae", _ptr(rewards), _ptr(values), _ptr(dones), _ptr(last_values), _ptr(returns), _ptr(advantages), T, N, float(gamma),
+               float(lam), int(bool(normalize)), _ptr(scratch), on=rewards)
 
 
 class PolicyChain:
@@ -1850,10 +1704,7 @@ class PolicyChain:
         for p in self._built:
             if p and not (p[0].is_cuda and p[0].is_contiguous() and p[0].dtype == torch.float32):
                 raise RuntimeError("PolicyChain: parameters must be contiguous fp32 ROCm tensors")
-        lib = _capi.load_library()
-        rc = lib.qa_mlp_pack(self.ops, self.n_ops, w, b, _ptr(self.packed), self.packed_floats, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"qa_mlp_pack failed with code {rc}: {lib.qa_last_error().decode()}")
+        API.launch("mlp_pack", self.ops, self.n_ops, w, b, _ptr(self.packed), self.packed_floats, on=dev)
 
     def forward(self, obs):
         """-> one (N, width) tensor per global output of the chain (policy chains: action mean, value).  The tensors are
@@ -1865,11 +1716,7 @@ class PolicyChain:
             bufs = [torch.zeros(n, w, device=obs.device) for w in self.out_widths]
             k = len(bufs)
             out = self._out[n] = (bufs, (C.c_void_p * k)(*[b.data_ptr() for b in bufs]), (C.c_int64 * k)(*self.out_widths))
-        lib = _capi.load_library()
-        rc = lib.qa_mlp_forward(_ptr(obs), obs.stride(0), n, obs.shape[1], self.ops, self.n_ops, _ptr(self.packed), out[1], out[2], len(out[0]),
-                                C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"qa_mlp_forward failed with code {rc}: {lib.qa_last_error().decode()}")
+        API.launch("mlp_forward", _ptr(obs), obs.stride(0), n, obs.shape[1], self.ops, self.n_ops, _ptr(self.packed), out[1], out[2], len(out[0]), on=obs)
         return tuple(out[0])
 
 

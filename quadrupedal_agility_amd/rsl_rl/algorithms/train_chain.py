@@ -20,6 +20,7 @@ import os
 import torch
 
 from quadrupedal_agility_amd import _capi
+from quadrupedal_agility_amd._capi import _ptr
 from quadrupedal_agility_amd.rsl_rl.algorithms import fused
 
 MAX_ROWS = int(os.environ.get("QA_TRAIN_CHAIN_MAX_ROWS", "8192"))      # measured (r6, profiles/r6_chain_steps.txt): 3,072-row steps 30 % faster, 6,144-row steps 17 % faster than the three-stream autograd step; 12,288 rows and up: slower
@@ -27,18 +28,8 @@ ENABLED = os.environ.get("QA_TRAIN_CHAIN", "1") != "0"
 DISC_ENABLED = os.environ.get("QA_DISC_TRAIN_CHAIN", "1") != "0"
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
 def _pad4(n):
     return (int(n) + 3) // 4 * 4
-
-
-def _ok(rc, name, prog):
-    if rc != 0:
-        msg = _capi.load_library().qa_last_error().decode() if prog.prefix == "qa_" else "(an injected library: no error text)"
-        raise RuntimeError(f"{prog.prefix}{name} failed with code {rc}: {msg}")
 
 
 class _Program:
@@ -47,13 +38,7 @@ class _Program:
     def __init__(self, lib=None, prefix="qa_"):
         self.ops, self.params, self.woff = [], [], 0
         self.packed = None
-        self.lib, self.prefix = lib, prefix          # injection point of the tests (another library exporting the same entry points under another prefix); the default is libqa_sim.so, and it is required
-
-    def _fn(self, name):
-        return getattr(self.lib or _capi.load_library(), self.prefix + name)
-
-    def _stream(self, t):
-        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else None
+        self.api = _capi.Api(lib, prefix)          # injection point of the tests (another library exporting the same entry points under another prefix); the default is libqa_sim.so, and it is required
 
     def _add(self, op, param):
         self.ops.append(op); self.params.append(param)
@@ -95,19 +80,18 @@ class _Program:
         self.w_ptrs = (C.c_void_p * self.n_ops)(*[(p[0].data_ptr() if p else None) for p in self.params])
         self.b_ptrs = (C.c_void_p * self.n_ops)(*[(p[1].data_ptr() if p and p[1] is not None else None) for p in self.params])
         for p in self.params:
-            if p and not ((p[0].is_cuda or self.prefix != "qa_") and p[0].is_contiguous() and p[0].dtype == torch.float32):
+            if p and not ((p[0].is_cuda or self.api.prefix != "qa_") and p[0].is_contiguous() and p[0].dtype == torch.float32):
                 raise RuntimeError("train chain: parameters must be contiguous fp32 ROCm tensors")
         dev = next(p[0] for p in self.params if p).device
         self.packed = torch.zeros(self.woff, dtype=torch.float32, device=dev)
 
     def pack(self):
-        _ok(self._fn("mlp_pack")(self.c_ops, self.n_ops, self.w_ptrs, self.b_ptrs, _ptr(self.packed), self.woff, self._stream(self.packed)), "mlp_pack", self)
+        self.api.launch("mlp_pack", self.c_ops, self.n_ops, self.w_ptrs, self.b_ptrs, _ptr(self.packed), self.woff, on=self.packed)
 
     def launch(self, x, x_cols, outs):
         k = len(outs)
         ptrs = (C.c_void_p * k)(*[o.data_ptr() for o in outs]); strides = (C.c_int64 * k)(*[o.stride(0) for o in outs])
-        _ok(self._fn("mlp_forward")(_ptr(x), x.stride(0), x.shape[0], x_cols, self.c_ops, self.n_ops, _ptr(self.packed), ptrs, strides, k, self._stream(x)),
-            "mlp_forward", self)
+        self.api.launch("mlp_forward", _ptr(x), x.stride(0), x.shape[0], x_cols, self.c_ops, self.n_ops, _ptr(self.packed), ptrs, strides, k, on=x)
 
 
 class _Packer:
@@ -136,7 +120,7 @@ class _Packer:
 
     def pack(self):
         for ops, n, w, b in self.calls:
-            _ok(self.prog._fn("mlp_pack")(ops, n, w, b, _ptr(self.buf), self.total, self.prog._stream(self.buf)), "mlp_pack", self.prog)
+            self.prog.api.launch("mlp_pack", ops, n, w, b, _ptr(self.buf), self.total, on=self.buf)
 
 
 class _Sides:
@@ -276,9 +260,9 @@ class PpoTrainChain:
         self._wg = []
         for lin_, _, _ in self.wgrads:
             n, k = lin_.out_features, lin_.in_features
-            nb = int(f._fn("linear_backward_weight_batch_scratch_bytes")(rows, k, n))
+            nb = int(f.api.fn("linear_backward_weight_batch_scratch_bytes")(rows, k, n))
             lay = (C.c_int64 * 5)()
-            _ok(f._fn("linear_backward_weight_batch_layout")(rows, k, n, lay), "linear_backward_weight_batch_layout", f)
+            f.api.call("linear_backward_weight_batch_layout", rows, k, n, lay)
             scratch = torch.zeros(nb // 4 + 4, dtype=torch.float32, device=dev)
             gw, gb = torch.zeros_like(lin_.weight), torch.zeros_like(lin_.bias)
             self._wg.append((scratch, nb, [int(v) for v in lay], gw, gb))
@@ -311,7 +295,7 @@ class PpoTrainChain:
             gt, xt = src[gs], src[xs]
             descs[i] = _capi.QaWgradDesc(gt.data_ptr() + 4 * g0, gt.stride(0), xt.data_ptr() + 4 * x0, xt.stride(0), None if defer else gw.data_ptr(),
                                          None if defer else gb.data_ptr(), self.rows, xk, gn, scratch.data_ptr(), nb)
-        _ok(self.bwd._fn("linear_backward_weight_batch")(descs, len(self.wgrads), self.bwd._stream(gin)), "linear_backward_weight_batch", self.bwd)
+        self.bwd.api.launch("linear_backward_weight_batch", descs, len(self.wgrads), on=gin)
         for (lin_, _, _), (scratch, nb, lay, gw, gb) in zip(self.wgrads, self._wg):
             lin_.weight.grad, lin_.bias.grad = gw, gb
             if defer:
@@ -395,7 +379,7 @@ class DiscTrainChain:
         # weight-gradient products: (rows, g tensor, g col, n, x tensor, x col, k)
         self._wg = {}
         for name, (r, n, k) in dict(w1=(rows, w1, k0), w2=(rows, w2, w1), wh=(rows, 8, w2), p1=(n_u, w1, k0), p2=(n_u, w2, w1), p3=(n_u, w2, 1)).items():
-            nb = int(f._fn("linear_backward_weight_batch_scratch_bytes")(r, k, n))
+            nb = int(f.api.fn("linear_backward_weight_batch_scratch_bytes")(r, k, n))
             self._wg[name] = (torch.zeros(nb // 4 + 4, dtype=torch.float32, device=dev), nb, z(n, k), z(n))
         return self
 
@@ -412,7 +396,7 @@ class DiscTrainChain:
             self._lay = {}
             for name, (r, n, k) in dict(w1=(R, w1, k0), w2=(R, w2, w1), wh=(R, 8, w2), p1=(U, w1, k0), p2=(U, w2, w1), p3=(U, w2, 1)).items():
                 lay = (C.c_int64 * 5)()
-                _ok(self.fwd._fn("linear_backward_weight_batch_layout")(r, k, n, lay), "linear_backward_weight_batch_layout", self.fwd)
+                self.fwd.api.call("linear_backward_weight_batch_layout", r, k, n, lay)
                 self._lay[name] = [int(v) for v in lay]
         return self._lay
 
@@ -463,7 +447,7 @@ class DiscTrainChain:
             scratch, nb, gw, gb = self._wg[name]
             descs[i] = _capi.QaWgradDesc(g.data_ptr() + 4 * g0, g.stride(0), x.data_ptr() + 4 * x0, x.stride(0), gw.data_ptr() if finish else None,
                                          gb.data_ptr() if finish else None, rows, k, n, scratch.data_ptr(), nb)
-        _ok(self.fwd._fn("linear_backward_weight_batch")(descs, len(jobs), self.fwd._stream(gin)), "linear_backward_weight_batch", self.fwd)
+        self.fwd.api.launch("linear_backward_weight_batch", descs, len(jobs), on=gin)
         (gw1, gb1), (gw2, gb2), (gwh, gbh) = (self._wg[k_][2:] for k_ in ("w1", "w2", "wh"))
         t1, t2, t3 = (self._wg[k_][2] for k_ in ("p1", "p2", "p3"))
         a = 2.0 * float(penalty_coef) / U
@@ -633,9 +617,9 @@ class TscTrainChain:
                        (e1, gcol("e1"), ("obs", 0, est_in)), (e2, gcol("e2"), tc("e1")), (e3, ("g_est", 0, n_exp), tc("e2"))]
         self._wg = []
         for lin_, (_, _, n), (_, _, k) in self.wgrads:
-            nb = int(f._fn("linear_backward_weight_batch_scratch_bytes")(rows, k, n))
+            nb = int(f.api.fn("linear_backward_weight_batch_scratch_bytes")(rows, k, n))
             lay = (C.c_int64 * 5)()
-            _ok(f._fn("linear_backward_weight_batch_layout")(rows, k, n, lay), "linear_backward_weight_batch_layout", f)
+            f.api.call("linear_backward_weight_batch_layout", rows, k, n, lay)
             self._wg.append((torch.zeros(nb // 4 + 4, dtype=torch.float32, device=dev), nb, [int(v) for v in lay], z(n, k), z(n)))
         return self
 
@@ -663,7 +647,7 @@ class TscTrainChain:
             gt, xt = src[gs], src[xs]
             descs[i] = _capi.QaWgradDesc(gt.data_ptr() + 4 * g0, gt.stride(0), xt.data_ptr() + 4 * x0, xt.stride(0), None if defer else gw.data_ptr(),
                                          None if defer else gb.data_ptr(), self.rows, xk, gn, scratch.data_ptr(), nb)
-        _ok(self.bwd._fn("linear_backward_weight_batch")(descs, len(self.wgrads), self.bwd._stream(dlogits)), "linear_backward_weight_batch", self.bwd)
+        self.bwd.api.launch("linear_backward_weight_batch", descs, len(self.wgrads), on=dlogits)
         hd, hc = self.ac.actor.actor_d, self.ac.actor.actor_c
         for (lin_, (_, _, n), (_, _, k)), (scratch, nb, lay, gw, gb) in zip(self.wgrads, self._wg):
             # the stacked heads' product: each head's gradient is a run of its rows -- of the finished product and of every part alike

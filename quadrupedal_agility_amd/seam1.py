@@ -24,33 +24,22 @@ _DT = {_capi.DTYPE_F32: torch.float32, _capi.DTYPE_I64: torch.int64, _capi.DTYPE
 
 class QaGym:
     def __init__(self, qcfg, device="cuda:0", lib=None):
-        self._prefix = "qa_"
-        if lib is not None:
-            self.lib, self._prefix = lib
-        else:
-            self.lib = _capi.load_library()
-            if not torch.cuda.is_available():
-                raise RuntimeError("QaGym needs a GPU: quadrupedal_agility_amd has no CPU fallback")
+        self.api = _capi.Api(*lib) if lib is not None else _capi.API
+        self.lib = self.api.lib
+        if lib is None and not torch.cuda.is_available():
+            raise RuntimeError("QaGym needs a GPU: quadrupedal_agility_amd has no CPU fallback")
         if not qcfg.export_body_state:
             raise ValueError("seam 1 needs qa_config.export_body_state = 1 (the env views rigid_body_state as (N, num_bodies, 13))")
         self.cfg, self.device = qcfg, torch.device(device)
-        n = self._fn("arena_bytes")(C.byref(qcfg))
+        n = self.api.fn("arena_bytes")(C.byref(qcfg))
         self._slab = torch.zeros(n + 256, dtype=torch.uint8, device=self.device)
         self.arena = self._slab[(-self._slab.data_ptr()) % 256:][:n]
         self.sim_handle = C.c_void_p()
-        rc = self._fn("create")(C.byref(qcfg), self.arena.data_ptr(), n, self._stream(), C.byref(self.sim_handle))
-        if rc != 0:
-            raise RuntimeError(f"qa_create failed with code {rc}")
+        self.api.call("create", C.byref(qcfg), self.arena.data_ptr(), n, self.api.stream(self.device), C.byref(self.sim_handle))
         self._tau = None
 
-    def _fn(self, name):
-        return getattr(self.lib, self._prefix + name)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.device.type == "cuda" else None
-
     def view(self, name):
-        off, shape, dt = _capi.tensor_info(self.lib, self._prefix, self.cfg, _capi.T[name])
+        off, shape, dt = _capi.tensor_info(self.lib, self.api.prefix, self.cfg, _capi.T[name])
         numel = 1
         for s in shape:
             numel *= s
@@ -75,9 +64,7 @@ class QaGym:
         self._tau = torques.contiguous()
 
     def simulate(self, sim):
-        rc = self._fn("simulate")(self.sim_handle, self._tau.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"qa_simulate failed with code {rc}")
+        self.api.launch("simulate", self.sim_handle, self._tau.data_ptr(), on=self.device)
 
     def fetch_results(self, sim, wait):
         pass                                  # results are already in the views

@@ -319,15 +319,12 @@ class LeggedRobot:
         self.common_step_counter += 1
         if self._glue_kernels():
             # r4: the counter's increment and the push as ONE launch (qa_tsc_push; Philox draws keyed by the step instead of torch's generator)
-            lib = _capi.load_library()
             if getattr(self, "_ticket", None) is None:
                 self._ticket = torch.zeros(1, dtype=torch.int32, device=self.device)
             d = cfg.domain_rand
-            rc = lib.qa_tsc_push(self.root_states.data_ptr(), self.num_envs, self._step_dev.data_ptr(), self._ticket.data_ptr(),
-                                 int(d.push_interval) if d.push_robots else 0, float(d.max_push_vel_xy), int(self.sim.cfg.seed) + 104729, int(self.sim.cfg.env_id_offset),
-                                 torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"qa_tsc_push failed with code {rc}: {lib.qa_last_error().decode()}")
+            _capi.API.launch("tsc_push", self.root_states.data_ptr(), self.num_envs, self._step_dev.data_ptr(), self._ticket.data_ptr(),
+                             int(d.push_interval) if d.push_robots else 0, float(d.max_push_vel_xy), int(self.sim.cfg.seed) + 104729, int(self.sim.cfg.env_id_offset),
+                             on=self.root_states)
         else:
             self._step_dev.add_(1)
             if cfg.domain_rand.push_robots:
@@ -357,15 +354,12 @@ class LeggedRobot:
         n_goal = cfg.obstacle.num_goals
         glue = self._glue_kernels() and flags.is_cuda
         if glue:
-            lib = _capi.load_library()
             if getattr(self, "_start_goal", None) is None:
                 self._start_goal = torch.zeros(self.num_envs, dtype=torch.long, device=self.device)
-            rc = lib.qa_tsc_start_pose(flags.data_ptr(), self.cur_obst_idx.data_ptr(), self.env_goals.data_ptr(), self.obst_angs.data_ptr(), self.num_envs,
-                                       int(self.env_goals.shape[1]), int(self.obstacle_types.shape[1]), int(n_goal), int(bool(ob.randomize_start)),
-                                       float(self.obstacle.frame_ang[0]), int(self.sim.cfg.seed) + 104729, self._step_dev.data_ptr(), int(self.sim.cfg.env_id_offset),
-                                       self._start_xy.data_ptr(), self._start_yaw.data_ptr(), self._start_goal.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"qa_tsc_start_pose failed with code {rc}: {lib.qa_last_error().decode()}")
+            _capi.API.launch("tsc_start_pose", flags.data_ptr(), self.cur_obst_idx.data_ptr(), self.env_goals.data_ptr(), self.obst_angs.data_ptr(), self.num_envs,
+                             int(self.env_goals.shape[1]), int(self.obstacle_types.shape[1]), int(n_goal), int(bool(ob.randomize_start)),
+                             float(self.obstacle.frame_ang[0]), int(self.sim.cfg.seed) + 104729, self._step_dev.data_ptr(), int(self.sim.cfg.env_id_offset),
+                             self._start_xy.data_ptr(), self._start_yaw.data_ptr(), self._start_goal.data_ptr(), on=flags)
             start_goal = self._start_goal
         elif ob.randomize_start:
             draw = torch.randint(0, self.obstacle_types.shape[1], (self.num_envs,), device=self.device)
@@ -388,12 +382,8 @@ class LeggedRobot:
             # and this code is replayed from a hipGraph -- no torch reduction in it (profiles/r2_hipgraph_stale_reductions.md)
             if getattr(self, "_any_reset", None) is None:
                 self._any_reset = torch.zeros(1, dtype=torch.uint8, device=self.device)
-            lib = _capi.load_library()
-            rc = lib.qa_tsc_reset_stats(flags.data_ptr(), bk.episode_sums_buf.data_ptr(), self.num_envs, bk.episode_sums_buf.shape[0],
-                                        float(self.max_episode_length_s), self._episode_means.data_ptr(), self._any_reset.data_ptr(),
-                                        torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"qa_tsc_reset_stats failed with code {rc}: {lib.qa_last_error().decode()}")
+            _capi.API.launch("tsc_reset_stats", flags.data_ptr(), bk.episode_sums_buf.data_ptr(), self.num_envs, bk.episode_sums_buf.shape[0],
+                             float(self.max_episode_length_s), self._episode_means.data_ptr(), self._any_reset.data_ptr(), on=flags)
             any_reset = self._any_reset
         else:
             f = (flags != 0).to(torch.float32)
@@ -410,18 +400,16 @@ class LeggedRobot:
             # _step_dev is common_step_counter's twin; the constructor's and every reset()'s extra post_physics_step put it ahead of global_counter
             self._oc.set_offset(self.common_step_counter - self.global_counter)
             if glue:
-                self._oc.launch(lib, self._step_dev, any_reset, torch.cuda.current_stream(self.device).cuda_stream)
+                self._oc.launch(_capi.API.lib, self._step_dev, any_reset, _capi.stream(flags))
             else:
                 self._oc.update_torch(self._step_dev, any_reset)
         if glue:
-            rc = lib.qa_tsc_reset_where(flags.data_ptr(), any_reset.data_ptr(), start_goal.data_ptr(), bk.cur_goal_idx.data_ptr(), bk.reach_goal_timer.data_ptr(),
-                                        bk.episode_sums_buf.data_ptr(), int(bk.episode_sums_buf.shape[0]), bk.episode_length_buf.data_ptr(), self.env_goals.data_ptr(),
-                                        int(self.env_goals.shape[1]), bk.cur_goals.data_ptr(), bk.next_goals.data_ptr(),
-                                        self.obst_state.data_ptr() if self.articulated else None, float(self.obstacle.seesaw_dof_pos) if self.articulated else 0.0,
-                                        self.cur_obst_idx.data_ptr(), self._seesaw_order.data_ptr() if (self.articulated and ob.randomize_start) else None,
-                                        self.num_envs, torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"qa_tsc_reset_where failed with code {rc}: {lib.qa_last_error().decode()}")
+            _capi.API.launch("tsc_reset_where", flags.data_ptr(), any_reset.data_ptr(), start_goal.data_ptr(), bk.cur_goal_idx.data_ptr(), bk.reach_goal_timer.data_ptr(),
+                             bk.episode_sums_buf.data_ptr(), int(bk.episode_sums_buf.shape[0]), bk.episode_length_buf.data_ptr(), self.env_goals.data_ptr(),
+                             int(self.env_goals.shape[1]), bk.cur_goals.data_ptr(), bk.next_goals.data_ptr(),
+                             self.obst_state.data_ptr() if self.articulated else None, float(self.obstacle.seesaw_dof_pos) if self.articulated else 0.0,
+                             self.cur_obst_idx.data_ptr(), self._seesaw_order.data_ptr() if (self.articulated and ob.randomize_start) else None,
+                             self.num_envs, on=flags)
         else:
             bk.reset_where(flags, start_goal)
             self._reset_articulated_obstacles(flags, any_reset)

@@ -143,9 +143,7 @@ class ObstacleCurriculum:
             self._args = a
         a = self._args
         a.step_counter, a.any_reset = step_dev.data_ptr(), any_reset.data_ptr()
-        rc = lib.qa_tsc_obstacle_curriculum(C.byref(a), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError(f"qa_tsc_obstacle_curriculum failed with code {rc}: {lib.qa_last_error().decode()}")
+        _capi.API.check("tsc_obstacle_curriculum", lib.qa_tsc_obstacle_curriculum(C.byref(a), stream))
 
     def update_torch(self, step_dev, any_reset):
         """the same update as tensor operations on the same lists and tables (no host read, no host branch)"""

@@ -40,13 +40,10 @@ class TaskLevelBookkeeping:
                  termination_contact_indices, num_bodies, device="cuda:0", lib=None):
         # `lib`: (library, symbol prefix) injected by the CPU tests, which drive this class with the oracle's twins on host
         # tensors; the product never passes it and loads the HIP library, which needs a GPU
-        self._prefix = "qa_"
-        if lib is not None:
-            self.lib, self._prefix = lib
-        else:
-            self.lib = _capi.load_library()
-            if not torch.cuda.is_available():
-                raise RuntimeError("TaskLevelBookkeeping needs a GPU: quadrupedal_agility_amd has no CPU fallback")
+        self.api = _capi.Api(*lib) if lib is not None else _capi.API
+        self.lib = self.api.lib
+        if lib is None and not torch.cuda.is_available():
+            raise RuntimeError("TaskLevelBookkeeping needs a GPU: quadrupedal_agility_amd has no CPU fallback")
         self.cfg, self.device = cfg, torch.device(device)
         dev = self.device
         self.dt = cfg.control.decimation * cfg.sim.dt
@@ -103,17 +100,6 @@ class TaskLevelBookkeeping:
             self.reward_scales[name] = float(getattr(cfg.rewards.scales, name)) * self.dt
             c.reward_scales[i] = self.reward_scales[name]
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.device.type == "cuda" else None
-
-    def _fn(self, name):
-        return getattr(self.lib, self._prefix + name)
-
-    def _check(self, rc, what):
-        if rc != 0:
-            err = self.lib.qa_last_error().decode() if hasattr(self.lib, "qa_last_error") else ""
-            raise RuntimeError(f"{what} failed with code {rc}: {err}")
-
     def _gather_cur_goals(self, future=0):
         """legged_robot.py:646-648"""
         idx = (self.cur_goal_idx[:, None, None] + future).clamp(0, self.env_goals.shape[1] - 1).expand(-1, -1, 3)
@@ -125,12 +111,11 @@ class TaskLevelBookkeeping:
         interval = max(1, int(self.cfg.commands.resampling_time / self.dt))
         if action_noise is not None:
             action_noise = action_noise.to(self.device, torch.float32).contiguous()
-        rc = self._fn("tsc_set_commands")(
-            actions.data_ptr(), self.episode_length_buf.data_ptr(), self.num_envs, self.num_actions_d, self.num_actions_c, self.dim_c,
+        self.api.launch(
+            "tsc_set_commands", actions.data_ptr(), self.episode_length_buf.data_ptr(), self.num_envs, self.num_actions_d, self.num_actions_c, self.dim_c,
             interval, self._mocap_index.ctypes.data, self._vel_ranges.ctypes.data, self._jump_range.ctypes.data,
             self._height_range.ctypes.data, action_noise.data_ptr() if action_noise is not None else None, self.commands.data_ptr(),
-            self.latent_eps.data_ptr(), self.latent_c.data_ptr(), self.next_commands.data_ptr(), self._stream())
-        self._check(rc, "qa_tsc_set_commands")
+            self.latent_eps.data_ptr(), self.latent_c.data_ptr(), self.next_commands.data_ptr(), on=self.device)
         return self.next_commands
 
     def post_physics_step(self, root_states, contact_forces, rigid_body_states, action_hl_history_buf=None, want_ids=True):
@@ -154,7 +139,7 @@ class TaskLevelBookkeeping:
                        rew_buf=self.rew_buf)
         for name, t in members.items():
             setattr(io, name, t.data_ptr())
-        self._check(self._fn("tsc_goal_step")(C.byref(self._cfg), C.byref(io), self._stream()), "qa_tsc_goal_step")
+        self.api.launch("tsc_goal_step", C.byref(self._cfg), C.byref(io), on=self.device)
         self.roll, self.pitch, self.yaw = self.rpy[:, 0], self.rpy[:, 1], self.rpy[:, 2]
         return self.reset_buf.nonzero(as_tuple=False).flatten() if want_ids else None          # nonzero() is a host sync
 
@@ -210,7 +195,7 @@ class TaskLevelBookkeeping:
         io = _capi.QaTscObsIo()
         for name in _capi.TSC_OBS_IO_FIELDS:
             setattr(io, name, members[name].data_ptr())
-        self._check(self._fn("tsc_observations")(C.byref(self._ocfg), C.byref(io), self._stream()), "qa_tsc_observations")
+        self.api.launch("tsc_observations", C.byref(self._ocfg), C.byref(io), on=self.device)
         return self.obs_buf
 
     def init_depth(self, height_samples, ceiling_samples, camera_pitch, seed=1, env_id_offset=0):
@@ -252,7 +237,7 @@ class TaskLevelBookkeeping:
             io.step_dev = step.data_ptr()
         else:
             self._dcfg.step = int(step)
-        self._check(self._fn("tsc_depth_update")(C.byref(self._dcfg), C.byref(io), self._stream()), "qa_tsc_depth_update")
+        self.api.launch("tsc_depth_update", C.byref(self._dcfg), C.byref(io), on=self.device)
         return self.depth_buffer
 
     def get_observations(self):

@@ -6,107 +6,70 @@ dicts load either way); the layout change is absorbed where the flattened activa
 
 The calls go through the C ABI (include/qa_sim.h, ABI 12); there is no fallback: on a GPU the stem either runs these kernels or raises.
 `ENABLED = False` (tests) sends the encoder through the aten / MIOpen modules for comparison."""
-import ctypes as C
-
 import torch
 
 from quadrupedal_agility_amd import _capi
 
 ENABLED = True
-_scratch = {}
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with code {rc}: {_capi.load_library().qa_last_error().decode()}")
-
-
-def _scratch_for(dev, nbytes):
-    """per device AND stream: two encoders running on two streams must not share partial sums"""
-    if torch.cuda.is_current_stream_capturing():
-        # a recording bakes the address in: the buffer must belong to the graph's pool, not to a cache that a later, larger request replaces
-        # (the old block would go back to the allocator under the graph's replays; ADVICE r3)
-        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    buf = _scratch.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-        _scratch[key] = buf
-    return buf
+API, _ptr = _capi.API, _capi._ptr
+SCRATCH_FLOOR = 1 << 20
 
 
 def stem_forward_raw(images, w1, b1, alpha=1.0):
     """(ELU(maxpool(conv5x5 + b)) channels-last [n][ph][pw][32], the pool's argmax bytes)"""
-    lib = _capi.load_library()
     n, ih, iw = images.shape
     ph, pw = (ih - 4) // 2, (iw - 4) // 2
     y = torch.empty(n, ph, pw, 32, dtype=torch.float32, device=images.device)
     am = torch.empty(n, ph, pw, 32, dtype=torch.uint8, device=images.device)
-    _check(lib.qa_depth_stem_forward(_ptr(images), _ptr(w1), _ptr(b1), _ptr(y), _ptr(am), n, ih, iw, float(alpha), _stream(images)), "qa_depth_stem_forward")
+    API.launch("depth_stem_forward", _ptr(images), _ptr(w1), _ptr(b1), _ptr(y), _ptr(am), n, ih, iw, float(alpha), on=images)
     return y, am
 
 
 def stem_backward_raw(images, argmax, grad_pre):
-    lib = _capi.load_library()
     n, ih, iw = images.shape
-    nb = lib.qa_depth_stem_backward_scratch_bytes()
-    sc = _scratch_for(images.device, nb)
+    sc = _capi.scratch_for(images.device, API.lib.qa_depth_stem_backward_scratch_bytes(), SCRATCH_FLOOR)
     out = torch.empty(832, dtype=torch.float32, device=images.device)
-    _check(lib.qa_depth_stem_backward(_ptr(images), _ptr(argmax), _ptr(grad_pre), _ptr(out), n, ih, iw, _ptr(sc), sc.numel(), _stream(images)), "qa_depth_stem_backward")
+    API.launch("depth_stem_backward", _ptr(images), _ptr(argmax), _ptr(grad_pre), _ptr(out), n, ih, iw, _ptr(sc), sc.numel(), on=images)
     return out
 
 
 def conv_forward_raw(x, w_khwc, bias, act, alpha=1.0):
     """act(conv(x, w) + bias): x [n][ih][iw][cin] channels-last, w [cout][kh][kw][cin]"""
-    lib = _capi.load_library()
     n, ih, iw, cin = x.shape
     cout, kh, kw, _ = w_khwc.shape
     y = torch.empty(n, ih - kh + 1, iw - kw + 1, cout, dtype=torch.float32, device=x.device)
-    _check(lib.qa_conv_nhwc_forward(_ptr(x), _ptr(w_khwc), _ptr(bias) if bias is not None else None, _ptr(y), n, ih, iw, cin, kh, kw, cout, int(act), float(alpha),
-                                    _stream(x)), "qa_conv_nhwc_forward")
+    API.launch("conv_nhwc_forward", _ptr(x), _ptr(w_khwc), _ptr(bias) if bias is not None else None, _ptr(y), n, ih, iw, cin, kh, kw, cout, int(act), float(alpha),
+               on=x)
     return y
 
 
 def conv_backward_input_raw(g_padded, w_flipped, x_act, act_prev, alpha=1.0):
     """conv(g_padded, w_flipped) * act'(x_act): g_padded [n][oh + 2 (kh-1)][ow + 2 (kw-1)][cout], w_flipped [cin][kh][kw][cout]"""
-    lib = _capi.load_library()
     n, ihp, iwp, cout = g_padded.shape
     cin, kh, kw, _ = w_flipped.shape
     gin = torch.empty(n, ihp - kh + 1, iwp - kw + 1, cin, dtype=torch.float32, device=g_padded.device)
-    _check(lib.qa_conv_nhwc_backward_input(_ptr(g_padded), _ptr(w_flipped), _ptr(x_act) if x_act is not None else None, _ptr(gin), n, ihp, iwp, cout, kh, kw, cin,
-                                           int(act_prev if x_act is not None else 0), float(alpha), _stream(g_padded)), "qa_conv_nhwc_backward_input")
+    API.launch("conv_nhwc_backward_input", _ptr(g_padded), _ptr(w_flipped), _ptr(x_act) if x_act is not None else None, _ptr(gin), n, ihp, iwp, cout, kh, kw, cin,
+               int(act_prev if x_act is not None else 0), float(alpha), on=g_padded)
     return gin
 
 
 def conv_backward_weight_raw(x, g, kh, kw):
     """(d loss / d w [cout][kh][kw][cin], d loss / d bias [cout]) from x [n][ih][iw][cin] and g [n][oh][ow][cout]"""
-    lib = _capi.load_library()
     n, ih, iw, cin = x.shape
     cout = g.shape[3]
-    nb = lib.qa_conv_nhwc_backward_weight_scratch_bytes(n, ih, iw, cin, kh, kw, cout)
-    sc = _scratch_for(x.device, nb)
+    sc = _capi.scratch_for(x.device, API.lib.qa_conv_nhwc_backward_weight_scratch_bytes(n, ih, iw, cin, kh, kw, cout), SCRATCH_FLOOR)
     gw = torch.empty(cout, kh, kw, cin, dtype=torch.float32, device=x.device)
     gb = torch.empty(cout, dtype=torch.float32, device=x.device)
-    _check(lib.qa_conv_nhwc_backward_weight(_ptr(x), _ptr(g), _ptr(gw), _ptr(gb), n, ih, iw, cin, kh, kw, cout, _ptr(sc), sc.numel(), _stream(x)),
-           "qa_conv_nhwc_backward_weight")
+    API.launch("conv_nhwc_backward_weight", _ptr(x), _ptr(g), _ptr(gw), _ptr(gb), n, ih, iw, cin, kh, kw, cout, _ptr(sc), sc.numel(), on=x)
     return gw, gb
 
 
 def elu_backward_pad_raw(g, y, pad, act=1, alpha=1.0):
     """(g * act'(y), the same with a zero border of `pad` pixels), both channels-last"""
-    lib = _capi.load_library()
     n, oh, ow, c = y.shape
     dy = torch.empty_like(y)
     dyp = torch.empty(n, oh + 2 * pad, ow + 2 * pad, c, dtype=torch.float32, device=y.device)
-    _check(lib.qa_elu_backward_pad(_ptr(g), _ptr(y), _ptr(dy), _ptr(dyp), n, oh, ow, c, int(pad), int(act), float(alpha), _stream(y)), "qa_elu_backward_pad")
+    API.launch("elu_backward_pad", _ptr(g), _ptr(y), _ptr(dy), _ptr(dyp), n, oh, ow, c, int(pad), int(act), float(alpha), on=y)
     return dy, dyp
 
 

@@ -180,11 +180,9 @@ class OnPolicyRunner:
         if tchain is not None:
             tchain.pack()                    # the weights changed in the last update(); one small launch per rollout
         if dchain is not None:
-            import ctypes as C
-            from quadrupedal_agility_amd import _capi
+            from quadrupedal_agility_amd._capi import API, _ptr as P
             from quadrupedal_agility_amd.rsl_rl.algorithms import fused
-            lib, disc, st, N = _capi.load_library(), self.discriminator, alg.storage, env.num_envs
-            P = lambda x: C.c_void_p(x.data_ptr())
+            disc, st, N = self.discriminator, alg.storage, env.num_envs
         for t in range(self.num_steps_per_env):
             #  the two history buffers swap ROLES on the host every step and a recording bakes both addresses in: with an odd number of
             # steps the newest history would end in the other buffer than the one the next replay starts reading -- the hybrid launch needs an even T
@@ -215,13 +213,10 @@ class OnPolicyRunner:
                 log_ptrs = (P(rs["cur"]), P(rs["fin_vals"][ts]), P(rs["fin_masks"][ts])) if logging else (None, None, None)
                 #  the reference bootstraps time-outs only when the env sends them (`'time_outs' in infos` <=> cfg.env.send_timeouts)
                 tout = env.bk.time_out_buf if "time_outs" in infos else self._no_timeouts(env)
-                rc = lib.qa_rollout_post_amp(P(rewards), P(dones.to(torch.int64)), P(tout), P(st.values[ts]), P(d), P(eps), P(logits), int(disc.dim_c),
-                                             P(rs["obs_bbc"]), int(rs["obs_bbc"].stride(0)), int(rs["obs_bbc"].shape[1]),
-                                             float(disc.reward_i_coef), float(disc.reward_us_coef), float(disc.reward_ss_coef), float(disc.reward_t_coef),
-                                             float(disc.dt), float(alg.gamma), N, P(st.rewards[ts]), P(st.dones[ts]), *log_ptrs,
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-                if rc != 0:
-                    raise RuntimeError(f"qa_rollout_post_amp failed with code {rc}: {lib.qa_last_error().decode()}")
+                API.launch("rollout_post_amp", P(rewards), P(dones.to(torch.int64)), P(tout), P(st.values[ts]), P(d), P(eps), P(logits), int(disc.dim_c),
+                           P(rs["obs_bbc"]), int(rs["obs_bbc"].stride(0)), int(rs["obs_bbc"].shape[1]),
+                           float(disc.reward_i_coef), float(disc.reward_us_coef), float(disc.reward_ss_coef), float(disc.reward_t_coef),
+                           float(disc.dt), float(alg.gamma), N, P(st.rewards[ts]), P(st.dones[ts]), *log_ptrs, on=rewards)
                 if logging:
                     if "episode" in infos:
                         ep_infos.append(infos["episode"])

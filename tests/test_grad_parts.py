@@ -187,3 +187,35 @@ def test_gradient_accumulation_over_backward_calls_and_preexisting_grads():
     assert fused.pending_grads() == 0
     ref(xs[0]).backward(gs[1])
     _close_grads(net, ref)
+
+
+@pytest.mark.gpu
+def test_launch_takes_the_current_stream_at_call_time():
+    """`fused.slab_sum` on the default stream, on a side stream and recorded into a graph: a launch sent to another stream than the capturing one
+    would not be in the graph, and the replay would leave the output stale.  Expected values: a plain left-to-right fp32 add in torch."""
+    from quadrupedal_agility_amd.rsl_rl import recording
+    from quadrupedal_agility_amd.rsl_rl.algorithms import fused
+
+    def values(shift):
+        base = torch.arange(96, dtype=torch.float32).reshape(3, 8, 4) * 0.37 + shift
+        return base * torch.tensor([1.0, 1.0e3, -1.0e-3]).view(3, 1, 1) + torch.tensor([0.1, -1000.3, 7.0e-4]).view(3, 1, 1)
+
+    def expected(p):
+        return (p[0] + p[1]) + p[2]
+
+    first, second = values(0.0), values(5.25)
+    assert not torch.equal(expected(first), expected(second))
+    parts = first.cuda()
+    on_default = fused.slab_sum(parts)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        on_side = fused.slab_sum(parts)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    assert torch.equal(on_default.cpu(), expected(first)) and torch.equal(on_side.cpu(), expected(first))
+    graph, recorded = recording.record(lambda: fused.slab_sum(parts))
+    parts.copy_(second)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(recorded.cpu(), expected(second))

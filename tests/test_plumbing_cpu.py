@@ -260,3 +260,54 @@ def test_data_parallel_pair_packs_reduces_and_applies_in_order(monkeypatch):
     log.clear()
     recording.replay_step(ga, None, None, None)          # a step recorded as one graph
     assert log == [("replay", ga)]
+
+
+# ------------------------------------------------------------------ the C-ABI call helper (_capi.Api)
+class _StandIn:
+    """what `_capi.Api` is handed in place of a library: entry points under a prefix, statuses as return values"""
+
+    def __init__(self, with_error_text):
+        self.seen = []
+        if with_error_text:
+            self.x_last_error = lambda: b"x_fail: the reason"
+
+    def x_ok(self, *args):
+        self.seen.append(args)
+        return 0
+
+    def x_fail(self, *args):
+        self.seen.append(args)
+        return -3
+
+
+def test_call_helper_returns_normally_on_a_zero_status():
+    from quadrupedal_agility_amd import _capi
+    lib = _StandIn(True)
+    api = _capi.Api(lib, "x_")
+    assert api.launch("ok", 1, 2.5, on=torch.device("cpu")) is None and api.call("ok", 7) is None
+    api.check("ok", 0)
+    assert lib.seen == [(1, 2.5, None), (7,)]
+
+
+@pytest.mark.parametrize("with_error_text", [True, False])
+def test_call_helper_raises_with_name_code_and_error_text(with_error_text):
+    from quadrupedal_agility_amd import _capi
+    api = _capi.Api(_StandIn(with_error_text), "x_")
+    text = "x_fail: the reason" if with_error_text else _capi.NO_ERROR_TEXT
+    for run in (lambda: api.launch("fail", 1, on=torch.zeros(2)), lambda: api.call("fail", 1), lambda: api.check("fail", -3)):
+        with pytest.raises(RuntimeError) as e:
+            run()
+        assert str(e.value) == f"x_fail failed with code -3: {text}"
+    assert _capi.NO_ERROR_TEXT == "(an injected library: no error text)"
+
+
+def test_call_helper_passes_no_stream_on_the_cpu_and_none_without_one():
+    from quadrupedal_agility_amd import _capi
+    lib = _StandIn(True)
+    api = _capi.Api(lib, "x_")
+    assert api.stream(torch.device("cpu")) is None and api.stream(torch.zeros(3)) is None
+    api.launch("ok", "a", on=torch.device("cpu"))
+    api.launch("ok", "b", on=torch.zeros(3))
+    api.call("ok", "c", 4)
+    assert lib.seen == [("a", None), ("b", None), ("c", 4)]          # the stream goes last; the no-stream variant appends nothing
+
