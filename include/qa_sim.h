@@ -834,7 +834,15 @@ int qa_disc_prepare(const float *const *batches, const int64_t *rows, int32_t nu
  *   act 7 / 8 / 9        forward: LeakyReLU(0.01) (x > 0 ? x : 0.01 x), SELU (lambda (x > 0 ? x : alpha (e^x - 1)), lambda = 1.0507009873554805,
  *                        alpha = 1.6732632423543772), sigmoid (1 / (1 + e^-x))
  *   act 10 / 11 / 12     their derivatives from the saved output y, used exactly as 4..6 are: y > 0 ? 1 : 0.01;  y > 0 ? lambda : y + lambda alpha;
- *                        y (1 - y).  A derivative code is its forward code + 3 (as 4..6 are for 1..3). */
+ *                        y (1 - y).  A derivative code is its forward code + 3 (as 4..6 are for 1..3).
+ * Global tensors within one launch: the ops of a program are ordered through the scratch buffers only (a launch of <= 2048 rows runs a tile's strands
+ * in separate workgroups, see qa_mlp_strands below, with nothing between them).  A program in which an op READS columns of outs[i] -- as its saved
+ * activation (aux), or through a QA_MLP_LOAD -- that an EARLIER op of the same program writes (a layer with dst_buf = -1, or QA_MLP_F_SAVE) is
+ * therefore REFUSED with QA_E_ARG by qa_mlp_forward, qa_mlp_strands and qa_mlp_groups (qa_mlp_pack does not look: its op list may hold the layers
+ * of several programs, whose slot numbers mean nothing to each other); what a later launch needs goes through a second launch (the training step's
+ * forward and backward programs).  Slots are told apart by index: two slots of one launch must not be the same memory where one is
+ * written and the other read.  A layer reads 16 * ceil-to-prefetch-depth(k / 16) source columns; those beyond k (the row's padding, the next row,
+ * the next buffer) are multiplied by the zero padding of the packed weights and may hold any FINITE value. */
 #define QA_MLP_ACT_NONE 0
 #define QA_MLP_ACT_ELU 1
 #define QA_MLP_ACT_RELU 2

@@ -2483,14 +2483,20 @@ int qo_mlp_pack(const qa_mlp_op *ops, int32_t num_ops, const float *const *weigh
 /* The partition of a chain into strands (include/qa_sim.h, ABI 15): checker-side restatement by label propagation.  Op i DEPENDS on op j < i when
  * i reads a scratch column whose most recent write before i was j's; a group is a connected set of ops, named by its earliest op; groups are dealt
  * largest cost first (ties: earliest group first) to the least loaded strand (ties: lowest strand).  cost(op) = k n for a layer, + 4096 per op. */
+static int qo_mlp_reads_own_output(const qa_mlp_op *ops, int32_t num_ops);
 int qo_mlp_strands(const qa_mlp_op *ops, int32_t num_ops, int32_t max_strands, int32_t *strand_of) {
     if (!ops || !strand_of || num_ops <= 0 || num_ops > QA_MLP_MAX_OPS || max_strands < 1) return QA_E_ARG;
+    if (qo_mlp_reads_own_output(ops, num_ops)) return QA_E_ARG;     /* strands order ops through the scratch buffers only */
     if (max_strands > 4) max_strands = 4;
     int label[QA_MLP_MAX_OPS];
     unsigned char dep[QA_MLP_MAX_OPS][QA_MLP_MAX_OPS];
     memset(dep, 0, sizeof(dep));
     for (int i = 0; i < num_ops; ++i) {
         label[i] = i; strand_of[i] = 0;
+        if (ops[i].kind == QA_MLP_GRAD && (ops[i].flags & QA_MLP_F_ADD) && ops[i].dst_buf > 0)       /* dst += ...: a read of what was there */
+            for (int c = ops[i].dst_col; c < ops[i].dst_col + ops[i].n; ++c)
+                for (int j = i - 1; j >= 0; --j)
+                    if (ops[j].dst_buf == ops[i].dst_buf && c >= ops[j].dst_col && c < ops[j].dst_col + ops[j].n) { dep[i][j] = 1; break; }
         if (ops[i].src_buf <= 0) continue;                       /* the input tile is everybody's */
         const int rd = ops[i].kind == QA_MLP_LAYER ? ops[i].k : ops[i].n;
         for (int c = ops[i].src_col; c < ops[i].src_col + rd; ++c)
@@ -2578,25 +2584,55 @@ int qo_mlp_groups(const qa_mlp_op *ops, int32_t num_ops, int32_t x_cols, int32_t
 static int qo_groups_setting = 2;
 int qo_mlp_set_groups(int32_t groups) { const int prev = qo_groups_setting; qo_groups_setting = groups >= 2 ? 2 : 1; return prev; }
 
+/* the derivative codes (act 4..6, 10..12): the activation's derivative from the forward layer's saved OUTPUT y, as include/qa_sim.h writes them */
+#define QO_SELU_LAMBDA 1.0507009873554805
+#define QO_SELU_ALPHA 1.6732632423543772
+static int qo_mlp_is_deriv(int act) { return (act >= QA_MLP_ACT_ELU_GRAD && act <= QA_MLP_ACT_TANH_GRAD) || (act >= QA_MLP_ACT_LRELU_GRAD && act <= QA_MLP_ACT_SIGMOID_GRAD); }
+static double qo_mlp_deriv(int act, float yf) {
+    const double y = yf;
+    switch (act) {
+        case QA_MLP_ACT_ELU_GRAD: return y > 0.0 ? 1.0 : y + 1.0;
+        case QA_MLP_ACT_RELU_GRAD: return y > 0.0 ? 1.0 : 0.0;
+        case QA_MLP_ACT_TANH_GRAD: return 1.0 - y * y;
+        case QA_MLP_ACT_LRELU_GRAD: return y > 0.0 ? 1.0 : 0.01;
+        case QA_MLP_ACT_SELU_GRAD: return y > 0.0 ? QO_SELU_LAMBDA : y + QO_SELU_LAMBDA * QO_SELU_ALPHA;
+        default: return y * (1.0 - y);                         /* QA_MLP_ACT_SIGMOID_GRAD */
+    }
+}
+/* include/qa_sim.h, "global tensors within one launch": 1 when an op reads (as its saved activation, or through a LOAD) columns of outs[i] that an
+ * earlier op of the program writes (a layer's global output, or QA_MLP_F_SAVE) -- a program the library refuses */
+static int qo_mlp_reads_own_output(const qa_mlp_op *ops, int32_t num_ops) {
+    for (int i = 0; i < num_ops; ++i) {
+        const int reads = ops[i].kind == QA_MLP_LOAD || ((ops[i].kind == QA_MLP_LAYER || ops[i].kind == QA_MLP_GRAD) && qo_mlp_is_deriv(ops[i].act));
+        if (!reads) continue;
+        for (int j = 0; j < i; ++j) {
+            const int writes = (ops[j].kind == QA_MLP_LAYER && ops[j].dst_buf < 0) || (ops[j].flags & QA_MLP_F_SAVE);
+            if (writes && ops[j].out_index == ops[i].aux_index && ops[j].out_col < ops[i].aux_col + ops[i].n && ops[i].aux_col < ops[j].out_col + ops[j].n) return 1;
+        }
+    }
+    return 0;
+}
+
 int qo_mlp_forward(const float *x, int64_t x_stride, int32_t rows, int32_t x_cols, const qa_mlp_op *ops, int32_t num_ops, const float *packed,
                    float *const *outs, const int64_t *out_strides, int32_t num_outs, void *stream) {
     (void)stream;
     static const int cols[4] = {QA_MLP_BUF0_COLS, QA_MLP_BUF1_COLS, QA_MLP_BUF2_COLS, QA_MLP_BUF3_COLS};
     if (!x || !ops || !packed || rows <= 0 || x_cols <= 0 || x_cols > cols[0] || num_ops <= 0 || num_ops > QA_MLP_MAX_OPS || num_outs < 0 ||
         num_outs > QA_MLP_MAX_OUTPUTS) return QA_E_ARG;
-    float *buf[4];
-    for (int b = 0; b < 4; ++b) buf[b] = (float *)malloc(sizeof(float) * (size_t)cols[b]);
+    if (qo_mlp_reads_own_output(ops, num_ops)) return QA_E_ARG;
+    float *buf[4];                                            /* every row has four padding columns behind it, which read as zero */
+    for (int b = 0; b < 4; ++b) buf[b] = (float *)malloc(sizeof(float) * (size_t)(cols[b] + 4));
     int rc = QA_OK;
     for (int64_t r = 0; r < rows && rc == QA_OK; ++r) {
-        for (int b = 0; b < 4; ++b) memset(buf[b], 0, sizeof(float) * (size_t)cols[b]);
+        for (int b = 0; b < 4; ++b) memset(buf[b], 0, sizeof(float) * (size_t)(cols[b] + 4));
         memcpy(buf[0], x + r * x_stride, sizeof(float) * (size_t)x_cols);
         for (int i = 0; i < num_ops; ++i) {
             const qa_mlp_op *o = &ops[i];
             if (o->src_buf < 0 || o->src_buf > 3 || o->dst_buf > 3 || o->n <= 0) { rc = QA_E_ARG; break; }
             const int save = (o->flags & QA_MLP_F_SAVE) != 0;
             if (save && (o->out_index < 0 || o->out_index >= num_outs || !outs || !outs[o->out_index] || out_strides[o->out_index] < o->out_col + o->n)) { rc = QA_E_ARG; break; }
-            const int deriv = (o->kind == QA_MLP_LAYER || o->kind == QA_MLP_GRAD) && o->act >= 4;
-            if (deriv && (o->act > 6 || o->aux_index < 0 || o->aux_index >= num_outs || !outs || !outs[o->aux_index] || out_strides[o->aux_index] < o->aux_col + o->n)) { rc = QA_E_ARG; break; }
+            const int deriv = (o->kind == QA_MLP_LAYER || o->kind == QA_MLP_GRAD) && qo_mlp_is_deriv(o->act);
+            if (deriv && (o->aux_index < 0 || o->aux_index >= num_outs || !outs || !outs[o->aux_index] || out_strides[o->aux_index] < o->aux_col + o->n)) { rc = QA_E_ARG; break; }
             const float *ysaved = deriv ? outs[o->aux_index] + r * out_strides[o->aux_index] + o->aux_col : NULL;
             if (o->kind == QA_MLP_LOAD) {                                 /* ABI 17: global -> scratch buffer */
                 if (o->dst_buf < 1 || o->dst_col + o->n > cols[o->dst_buf] || o->aux_index < 0 || o->aux_index >= num_outs || !outs || !outs[o->aux_index] ||
@@ -2614,13 +2650,14 @@ int qo_mlp_forward(const float *x, int64_t x_stride, int32_t rows, int32_t x_col
                         double v = buf[o->src_buf][o->src_col + c];
                         if (o->flags & QA_MLP_F_ADD) v = (double)(float)v + (double)buf[o->dst_buf][o->dst_col + c];
                         float f = (float)v;
-                        if (deriv) { const float y = ysaved[c]; f *= o->act == 4 ? (y > 0.0f ? 1.0f : y + 1.0f) : o->act == 5 ? (y > 0.0f ? 1.0f : 0.0f) : (1.0f - y * y); }
+                        if (deriv) f = (float)((double)f * qo_mlp_deriv(o->act, ysaved[c]));
                         buf[o->dst_buf][o->dst_col + c] = f;
                     }
                 if (save) memcpy(outs[o->out_index] + r * out_strides[o->out_index] + o->out_col, buf[o->dst_buf] + o->dst_col, sizeof(float) * (size_t)o->n);
                 continue;
             }
-            if (o->kind != QA_MLP_LAYER || o->src_col + o->k > cols[o->src_buf] || o->dst_buf == o->src_buf || o->dst_buf == 0 ||
+            if (o->kind != QA_MLP_LAYER || o->k <= 0 || o->src_col < 0 || o->src_col + o->k > cols[o->src_buf] + 4 || o->act < 0 || o->act > QA_MLP_ACT_SIGMOID_GRAD ||
+                o->dst_buf == o->src_buf || o->dst_buf == 0 ||
                 (o->dst_buf > 0 && o->dst_col + o->n > cols[o->dst_buf]) ||
                 (o->dst_buf < 0 && (o->out_index < 0 || o->out_index >= num_outs || !outs || !outs[o->out_index]))) { rc = QA_E_ARG; break; }
             const float *w = packed + o->w_off, *bias = packed + o->b_off, *in = buf[o->src_buf] + o->src_col;
@@ -2631,7 +2668,10 @@ int qo_mlp_forward(const float *x, int64_t x_stride, int32_t rows, int32_t x_col
                 if (o->act == 1) v = v > 0.0f ? v : (float)(exp((double)v) - 1.0);
                 else if (o->act == 2) v = v > 0.0f ? v : 0.0f;
                 else if (o->act == 3) v = (float)tanh((double)v);
-                else if (deriv) { const float y = ysaved[c]; v = (float)(acc * (o->act == 4 ? (y > 0.0f ? 1.0 : (double)y + 1.0) : o->act == 5 ? (y > 0.0f ? 1.0 : 0.0) : 1.0 - (double)y * y)); }
+                else if (o->act == QA_MLP_ACT_LRELU) v = v > 0.0f ? v : (float)(0.01 * (double)v);
+                else if (o->act == QA_MLP_ACT_SELU) v = (float)(QO_SELU_LAMBDA * (v > 0.0f ? (double)v : QO_SELU_ALPHA * (exp((double)v) - 1.0)));
+                else if (o->act == QA_MLP_ACT_SIGMOID) v = (float)(1.0 / (1.0 + exp(-(double)v)));
+                else if (deriv) v = (float)(acc * qo_mlp_deriv(o->act, ysaved[c]));
                 if (o->dst_buf > 0) buf[o->dst_buf][o->dst_col + c] = v;
                 if (o->dst_buf < 0 || save) outs[o->out_index][r * out_strides[o->out_index] + o->out_col + c] = v;
             }

@@ -522,8 +522,29 @@ static int mlp_check(const qa_mlp_op *ops, int32_t num_ops, const char *who) {
     return QA_OK;
 }
 
+/* Global tensors within one launch (include/qa_sim.h): the strands of a tile are separate workgroups ordered by nothing but the scratch buffers
+ * each of them owns, so an op must not read (as its saved activation, or through a LOAD) columns of outs[i] that an earlier op of the program
+ * writes.  Checked where the op list is a program to be RUN (qa_mlp_forward, qa_mlp_strands, qa_mlp_groups); qa_mlp_pack takes the layers of several
+ * programs in one list (a step's forward and backward halves share one packed buffer), where slot numbers of different programs mean nothing to each other. */
+static int mlp_check_program(const qa_mlp_op *ops, int32_t num_ops, const char *who) {
+    int rc = mlp_check(ops, num_ops, who);
+    if (rc != QA_OK) return rc;
+    for (int i = 0; i < num_ops; ++i) {
+        const qa_mlp_op &o = ops[i];
+        if (!(o.kind == QA_MLP_LOAD || ((o.kind == QA_MLP_LAYER || o.kind == QA_MLP_GRAD) && mlp_is_grad(o.act)))) continue;
+        for (int j = 0; j < i; ++j) {
+            const qa_mlp_op &w = ops[j];
+            const bool writes = (w.kind == QA_MLP_LAYER && w.dst_buf < 0) || (w.flags & QA_MLP_F_SAVE);
+            if (writes && w.out_index == o.aux_index && w.out_col < o.aux_col + o.n && o.aux_col < w.out_col + w.n) {
+                snprintf(g_perr, sizeof(g_perr), "%s: op %d reads columns %d..%d of output %d, which op %d of the same program writes", who, i, o.aux_col,
+                         o.aux_col + o.n - 1, o.aux_index, j); return QA_E_ARG; }
+        }
+    }
+    return QA_OK;
+}
+
 int qa_mlp_strands(const qa_mlp_op *ops, int32_t num_ops, int32_t max_strands, int32_t *strand_of) {
-    int rc = mlp_check(ops, num_ops, "qa_mlp_strands");
+    int rc = mlp_check_program(ops, num_ops, "qa_mlp_strands");
     if (rc != QA_OK) return rc;
     if (!strand_of || max_strands < 1) { snprintf(g_perr, sizeof(g_perr), "qa_mlp_strands: bad argument"); return QA_E_ARG; }
     return mlp_strands(ops, num_ops, max_strands > 4 ? 4 : max_strands, strand_of);
@@ -550,7 +571,7 @@ int qa_mlp_set_groups(int32_t groups) {
 }
 
 int qa_mlp_groups(const qa_mlp_op *ops, int32_t num_ops, int32_t x_cols, int32_t *strand_of, int32_t *base, int32_t *stride, int32_t *lds_floats) {
-    int rc = mlp_check(ops, num_ops, "qa_mlp_groups");
+    int rc = mlp_check_program(ops, num_ops, "qa_mlp_groups");
     if (rc != QA_OK) return rc;
     if (!strand_of || !base || !stride || !lds_floats || x_cols <= 0 || x_cols > QA_MLP_BUF0_COLS) { snprintf(g_perr, sizeof(g_perr), "qa_mlp_groups: bad argument"); return QA_E_ARG; }
     MlpArgs a{};
@@ -582,7 +603,7 @@ int qa_mlp_pack(const qa_mlp_op *ops, int32_t num_ops, const float *const *weigh
 
 int qa_mlp_forward(const float *x, int64_t x_stride, int32_t rows, int32_t x_cols, const qa_mlp_op *ops, int32_t num_ops, const float *packed,
                    float *const *outs, const int64_t *out_strides, int32_t num_outs, void *stream) {
-    int rc = mlp_check(ops, num_ops, "qa_mlp_forward");
+    int rc = mlp_check_program(ops, num_ops, "qa_mlp_forward");
     if (rc != QA_OK) return rc;
     if (!x || !packed || rows <= 0 || x_cols <= 0 || x_cols > QA_MLP_BUF0_COLS || x_stride < x_cols || num_outs < 0 || num_outs > QA_MLP_MAX_OUTPUTS ||
         (num_outs > 0 && (!outs || !out_strides))) { snprintf(g_perr, sizeof(g_perr), "qa_mlp_forward: bad argument"); return QA_E_ARG; }

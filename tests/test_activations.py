@@ -19,6 +19,7 @@ from quadrupedal_agility_amd import _capi
 from quadrupedal_agility_amd.rsl_rl.algorithms import fused, train_chain
 from quadrupedal_agility_amd.rsl_rl.algorithms.fused import PolicyChain
 from quadrupedal_agility_amd.rsl_rl.modules import ActorCritic, Estimator, get_activation
+from tests.oracle_lib import load_oracle
 
 DIMS = dict(num_prop=57, num_hist=10, num_explicit=4, num_latent=29, num_command=11)
 N_OBS = 57 + 4 + 29 + 570 + 11
@@ -41,18 +42,6 @@ def modules(name, seed=0, hidden=(512, 256, 128)):
     return ac, est
 
 
-class _HostEntryPoints:
-    """libqa_sim.so's host-only entry points under the prefix train_chain's injection point expects from "another library": the descriptions are
-    built on CPU tensors here, and the oracle's twins reject the new codes"""
-
-    def __init__(self):
-        self.lib = _capi.load_library()
-
-    def __getattr__(self, name):
-        assert name.startswith("qo_"), name
-        return getattr(self.lib, "qa_" + name[3:])
-
-
 def _layer_acts(ops):
     return [op.act for op in ops if op.kind == _capi.MLP_LAYER or op.kind == _capi.MLP_GRAD]
 
@@ -72,7 +61,7 @@ def test_descriptions_accept_uniform_policies(name):
         assert lib.qa_mlp_packed_floats(chain.ops, chain.n_ops) == chain.packed_floats
         strands = (C.c_int32 * chain.n_ops)()
         assert lib.qa_mlp_strands(chain.ops, chain.n_ops, 4, strands) >= 1, lib.qa_last_error().decode()      # the library's own validation takes the codes
-    tc = train_chain.PpoTrainChain.describe(ac, est, 64, lib=_HostEntryPoints(), prefix="qo_")
+    tc = train_chain.PpoTrainChain.describe(ac, est, 64, lib=load_oracle(), prefix="qo_")
     assert tc is not None, name
     fwd, bwd = _layer_acts(tc.fwd.ops), _layer_acts(tc.bwd.ops)
     assert sorted(a for a in fwd if a) == [code] * 10 and fwd.count(0) == 3, (name, fwd)
@@ -88,11 +77,11 @@ def test_descriptions_decline_mixed_stacks_and_other_slopes():
     ac, est = modules("tanh")
     ac.actor_trunk[3] = torch.nn.Sigmoid()
     assert PolicyChain.describe(ac, est, True) is None
-    assert train_chain.PpoTrainChain.describe(ac, est, 64, lib=_HostEntryPoints(), prefix="qo_") is None
+    assert train_chain.PpoTrainChain.describe(ac, est, 64, lib=load_oracle(), prefix="qo_") is None
     ac, est = modules("tanh")
     est2 = Estimator(57, 4, hidden_dims=[128, 64], activation="selu")
     assert PolicyChain.describe(ac, est2, True) is None and PolicyChain.describe(ac, est2, False) is not None
-    assert train_chain.PpoTrainChain.describe(ac, est2, 64, lib=_HostEntryPoints(), prefix="qo_") is None
+    assert train_chain.PpoTrainChain.describe(ac, est2, 64, lib=load_oracle(), prefix="qo_") is None
     ac, est = modules("lrelu")
     ac.critic_trunk[1] = torch.nn.LeakyReLU(0.2)            # not the reference's slope
     assert PolicyChain.describe(ac, est, True) is None
