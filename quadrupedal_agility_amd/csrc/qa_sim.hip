@@ -18,8 +18,10 @@
 
 #include "../../include/qa_sim.h"
 #include "../../include/qa_sim_curriculum.h"
+#include "../../include/qa_sim_rewards.h"
 #include "qa_go2_model.h"
 #include "qa_physics.h"
+#include "qa_rewards.h"
 
 #define QA_BLOCK 64
 #define ENVS_PER_BLOCK (QA_BLOCK / 4)
@@ -101,6 +103,11 @@ struct Ptrs {
     const float *terrain_origins;
     int32_t terrain_rows, terrain_cols;
     float terrain_env_length, terrain_episode_s;
+    // qa_set_extra_rewards (include/qa_sim_rewards.h): caller-owned buffers and the terms' scalars; xr_sums null = the feature is off
+    float *xr_sums, *xr_air, *xr_stats;
+    const float *xr_scan;
+    int32_t xr_scan_n;
+    float xr_scale[QA_NUM_EXTRA_REWARDS], xr_target, xr_max_force, xr_dt;
 };
 
 struct qa_sim {
@@ -471,6 +478,7 @@ struct PostIn {
     // for the ~2 us of each round trip
     float last_act[3], last_torg[3], last_qd[3], esum[QA_NUM_REWARDS];
     float cmd[5], latc[5], eps; int64_t epl0; uint8_t last_contact;
+    float xsum[QA_NUM_EXTRA_REWARDS], air;      // qa_set_extra_rewards: the running extra sums and this leg's air time (post_in_preload_extra)
 };
 // (the height-field build has no registers to spare for these ~40 values across the substeps -- they would spill to scratch -- and loads them
 // right in front of the post-physics phase, as r4 did)
@@ -487,7 +495,37 @@ QA_DEV void post_in_preload(PostIn &in, const Ptrs &p, int env, int leg, int N) 
     in.eps = p.latent_eps[env]; in.epl0 = p.episode_length[env]; in.last_contact = p.last_contacts[(int64_t)env * 4 + leg];
 }
 
-template <bool PLANE, int LPE, int LEAN = 0, int HELP = 0>
+// What the extra reward terms (include/qa_sim_rewards.h) read of the previous step, in the XR instantiations (below).  Not part of
+// post_in_preload: the plane kernels call that in FRONT of the physics, where eleven more values would be held across the substeps; this runs
+// right in front of the post-physics phase, one more round trip on the opted-in path only.
+template <int XR>
+QA_DEV void post_in_preload_extra(PostIn &in, const Ptrs &p, int env, int leg, int N) {
+    if (XR) {
+#pragma unroll
+        for (int r = 0; r < QA_NUM_EXTRA_REWARDS; ++r) in.xsum[r] = p.xr_sums[(int64_t)r * N + env];
+        in.air = p.xr_air[(int64_t)env * 4 + leg];
+    }
+}
+
+// measured_heights (legged_robot.py:1190-1228) at ONE point (vx, vy) of the scan grid, given in the base's yaw frame: scan_center_height's lookup
+// (qa_physics.h) for any point.  The cell is clamped to the field, so no offset can index outside HEIGHT_SAMPLES.
+QA_DEV float scan_point_height(const TerrainView &T, V3 pos, float qz, float qw, float vx, float vy) {
+    float nrm = fmaxf(sqrtf(qz * qz + qw * qw), 1e-9f);
+    qz /= nrm; qw /= nrm;
+    float tx = -qz * vy * 2.0f, ty = qz * vx * 2.0f;
+    float px = vx + qw * tx - qz * ty + pos.x, py = vy + qw * ty + qz * tx + pos.y;
+    px += T.border; py += T.border;
+    int ix = (int)(px / T.hscale), iy = (int)(py / T.hscale);
+    ix = min(max(ix, 0), T.rows - 2); iy = min(max(iy, 0), T.cols - 2);
+    const int16_t *g = T.samples + (int64_t)ix * T.cols + iy;
+    int a = g[0], b = g[T.cols], d = g[1];
+    return (float)min(min(a, b), d) * T.vscale;
+}
+
+// XR = 1: the instantiations qa_set_extra_rewards switches the launches to.  A template flag, not a uniform branch on p.xr_sums as the terrain
+// curriculum's: with the branch the compiler if-converted the reward phase (both summations computed, results selected), which changed how the
+// DEFAULT path's multiply-adds contract -- the XR = 0 instantiations are instruction for instruction the kernels without the feature.
+template <bool PLANE, int LPE, int LEAN = 0, int HELP = 0, int XR = 0>
 __device__ __forceinline__ void post_physics_phase(const qa_config &c, const Ptrs &p, const MocapIdx &mi, long long *qa_prof, PostIn &in, const TerrainView &T,
                                                    const float *tbl, float *s_stage, float *s_rows, const int tix, const int bix, const int env,
                                                    const int leg, const bool valid, const bool owner, const int le, const int64_t step, f4 *mail = nullptr) {
@@ -511,6 +549,7 @@ __device__ __forceinline__ void post_physics_phase(const qa_config &c, const Ptr
     const float ffn = sqrtf(dot(foot_f, foot_f));
     const uint8_t contact = ffn > 2.0f;
     const uint8_t cfilt = contact | in.last_contact;
+    uint8_t contact_out = contact;               // LAST_CONTACTS of this step (feet_air_time of the extra rewards overwrites it, legged_robot.py:1342)
 
     // commands / latents in registers (replicated)
     float cmd[5], eps; int gait = 0;
@@ -587,12 +626,48 @@ __device__ __forceinline__ void post_physics_phase(const qa_config &c, const Ptr
     }
     float rew = 0.f;
     float esum[QA_NUM_REWARDS];
+    float xsum_[QA_NUM_EXTRA_REWARDS], air = 0.f;
+    if (XR) {          // qa_set_extra_rewards
+        float xt[QA_NUM_EXTRA_REWARDS];
+        xt[QA_XR_ANG_VEL_XY] = qa_rw_ang_vel_xy(bav.x, bav.y);
+        float mean_h = st.pos.z;                     // the scan is 0 (plane, or no measured heights)
+        if (!PLANE) {
+            const int ns = p.xr_scan_n;
+            if (ns > 0) {
+                float s = 0.f;
+                for (int i = leg; i < ns; i += LPE) s += st.pos.z - scan_point_height(T, st.pos, st.qz, st.qw, p.xr_scan[2 * i], p.xr_scan[2 * i + 1]);
+                mean_h = xsum<LPE>(s) / (float)ns;
+            }
+        }
+        xt[QA_XR_BASE_HEIGHT] = qa_rw_base_height(mean_h, p.xr_target);
+        xt[QA_XR_DOF_VEL] = xsum<LPE>(qa_rw_dof_vel_leg(st.qd[0], st.qd[1], st.qd[2]));
+        const float cnorm = qa_rw_command_norm(cmd[0], cmd[1]);
+        air = in.air;
+        xt[QA_XR_FEET_AIR_TIME] = 0.f;
+        if (p.xr_scale[QA_XR_FEET_AIR_TIME] != 0.0f) {      // the reference only calls (and its side effects only happen for) terms with a scale
+            const bool contact_z = foot_f.z > 1.0f;
+            xt[QA_XR_FEET_AIR_TIME] = xsum<LPE>(qa_rw_feet_air_time_leg(&air, contact_z, contact != 0, p.xr_dt)) * qa_rw_moving(cnorm);
+            contact_out = contact_z;
+        }
+        xt[QA_XR_FEET_CONTACT_FORCES] = xsum<LPE>(qa_rw_feet_contact_forces_leg(foot_f.x, foot_f.y, foot_f.z, p.xr_max_force));
+        xt[QA_XR_FEET_STUMBLE] = xor_<LPE>(qa_rw_feet_stumble_leg(foot_f.x, foot_f.y, foot_f.z)) ? 1.0f : 0.0f;
+        xt[QA_XR_LIN_VEL_Z] = qa_rw_lin_vel_z(blv.z);
+        xt[QA_XR_ORIENTATION] = qa_rw_orientation(pg.x, pg.y);
+        xt[QA_XR_STAND_STILL] = xsum<LPE>(qa_rw_stand_still_leg(st.q[0], st.q[1], st.q[2], q0[0], q0[1], q0[2])) * qa_rw_standing(cnorm);
+        xt[QA_XR_TERMINATION] = qa_rw_termination(reset, timeout);
+#pragma unroll
+        for (int r = 0; r < QA_NUM_REWARDS; ++r) esum[r] = in.esum[r];
+#pragma unroll
+        for (int r = 0; r < QA_NUM_EXTRA_REWARDS; ++r) xsum_[r] = in.xsum[r];
+        rew = qa_rw_total(term, c.reward_scale_dt, esum, xt, p.xr_scale, xsum_, c.only_positive_rewards);
+    } else {
 #pragma unroll
     for (int r = 0; r < QA_NUM_REWARDS; ++r) {
         esum[r] = in.esum[r];
         if (c.reward_scale_dt[r] != 0.0f) { float v = term[r] * c.reward_scale_dt[r]; rew += v; esum[r] += v; }
     }
     if (c.only_positive_rewards) rew = fmaxf(rew, 0.f);
+    }
 
     QA_STAMP(6);
     wave_lds_sync();          // physics scratch is dead from here on; the staging area takes its place
@@ -610,6 +685,15 @@ __device__ __forceinline__ void post_physics_phase(const qa_config &c, const Ptr
                 esum[r] = 0.f;
             }
             if (leg == 0 && valid) atomicAdd(&p.episode_stats[16 * (step & 1) + 14], 1.0f);
+            if (XR) {      // reset_idx :224, :231-234 for the extra terms
+#pragma unroll
+                for (int r = 0; r < QA_NUM_EXTRA_REWARDS; ++r) {
+                    if ((r & 3) == leg && valid) atomicAdd(&p.xr_stats[16 * (step & 1) + r], xsum_[r]);
+                    xsum_[r] = 0.f;
+                }
+                if (leg == 0 && valid) atomicAdd(&p.xr_stats[16 * (step & 1) + 14], 1.0f);
+                air = 0.f;
+            }
             if (!PLANE) {
                 float org[3] = {p.env_origins[3 * env], p.env_origins[3 * env + 1], p.env_origins[3 * env + 2]};
                 if (p.terrain_levels) update_terrain_level(c, p, env, leg, valid, step, st.pos, cmd, org);      // uniform over the launch
@@ -697,6 +781,11 @@ __device__ __forceinline__ void post_physics_phase(const qa_config &c, const Ptr
             }
         }
     }
+    if (XR && valid) {      // the extra terms' state: stored by the env's own lanes (the mailed record of write_scalars has no room for it)
+        p.xr_air[(int64_t)env * 4 + leg] = air;
+#pragma unroll
+        for (int r = 0; r < QA_NUM_EXTRA_REWARDS; ++r) if ((r & 3) == leg) p.xr_sums[(int64_t)r * N + env] = xsum_[r];
+    }
     QA_STAMP(8);
     // ---- per-env scalars and small rows, written by the quad (write_scalars).  With helper wavefronts the ~45 scattered dword stores -- 9.7 k of the
     // launch's 112 k cycles on a wavefront that has nothing else to issue -- go through the mail to the contact helper, which is idle by now
@@ -715,7 +804,7 @@ __device__ __forceinline__ void post_physics_phase(const qa_config &c, const Ptr
         w[SO_CMDDIRTY] = __int_as_float(cmd_dirty ? 1 : 0); w[SO_GAIT] = __int_as_float(gait); w[SO_EPS] = eps;
 #pragma unroll
         for (int i = 0; i < 5; ++i) w[SO_CMD + i] = cmd[i];
-        w[SO_FFN] = ffn; w[SO_CONTACT] = __int_as_float((int)contact); w[SO_CFILT] = __int_as_float((int)cfilt);
+        w[SO_FFN] = ffn; w[SO_CONTACT] = __int_as_float((int)contact_out); w[SO_CFILT] = __int_as_float((int)cfilt);
 #pragma unroll
         for (int r = 0; r < QA_NUM_REWARDS; ++r) w[SO_ESUM + r] = esum[r];
         if (HELP) {
@@ -818,8 +907,9 @@ QA_DEV void shift_history_store(const Ptrs &p, int bix, int lane, int N, float (
 // whose own post_physics_step (goals, termination, rewards, reset, three observation rows) are separate kernels (qa_tsc_*).
 // HELP = 1 (plane kernels): two helper wavefronts per workgroup take the bias forces and the contact candidates of every substep off the env's own
 // wavefront (phys_substep ROLE 1 / 2 / 3, qa_physics.h) -- three of a CU's four SIMDs idle otherwise at one wavefront per CU.
-template <bool PLANE, int LPE, int MODE = 0, int LEAN = 0, int HELP = 0>
+template <bool PLANE, int LPE, int MODE = 0, int LEAN = 0, int HELP = 0, int XR = 0>
 __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(StepArgs a) {
+    static_assert(XR == 0 || MODE == 0, "the extra reward terms belong to the behaviour-level post-physics phase");
     static_assert(LEAN == 0 || MODE == 0, "the task-level tree reads every tensor the physics step exports");
     static_assert(HELP == 0 || (PLANE && MODE == 0), "helper wavefronts: the behaviour-level plane kernels");
     constexpr int WPB = 1;                             // env groups (wavefronts with envs of their own) per workgroup
@@ -916,6 +1006,7 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
     const int64_t step = a.step_ptr ? *a.step_ptr : a.step;
 
     if (bix == 0 && tix < 16) p.episode_stats[16 * ((step + 1) & 1) + tix] = 0.f;   // next step's bin
+    if (XR && bix == 0 && tix < 16) p.xr_stats[16 * ((step + 1) & 1) + tix] = 0.f;
 
     // ---- action history roll, delay, clip (legged_robot.py:84-98); lane handles its 3 joints
     float act[3], raw_act[3];
@@ -1130,10 +1221,11 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
     }
     QA_STAMP(4);
     if (!PLANE) post_in_preload(in, p, env, leg, N);
+    post_in_preload_extra<XR>(in, p, env, leg, N);
     in.st = st; in.foot_f = co.foot_f; in.hip_f = hip_f; in.thigh_f = thigh_f; in.calf_f = calf_f; in.base_f = base_f; in.foot_w = foot_w; in.fric = fric;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { in.act[k] = act[k]; in.raw_act[k] = raw_act[k]; in.tau[k] = tau[k]; in.tau_org[k] = tau_org[k]; in.sp[k] = sp[k]; in.sd[k] = sd[k]; in.fimp[k] = fimp[k]; }
-    post_physics_phase<PLANE, LPE, LEAN, HELP>(c, p, a.mi, a.prof, in, T, tbl, s_stage, s_rows, tix, bix, env, leg, valid, owner, le, step, mail);
+    post_physics_phase<PLANE, LPE, LEAN, HELP, XR>(c, p, a.mi, a.prof, in, T, tbl, s_stage, s_rows, tix, bix, env, leg, valid, owner, le, step, mail);
     // the device-side step counter advances once every wavefront of the launch is done with it (they all read it at their
     // start): the last one to arrive resets the arrival counter and bumps the step -- no separate 1-thread launch per env step
     if (a.step_ptr && tix == 0) {
@@ -1144,7 +1236,7 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
 }
 
 // post_physics_step alone, from the arena (qa_debug_post_physics): the PostIn record is loaded instead of computed
-template <bool PLANE>
+template <bool PLANE, int XR = 0>
 __global__ void __launch_bounds__(QA_BLOCK) qa_post_physics_kernel(StepArgs a) {
     constexpr int LPE = 4, EPB = QA_BLOCK / LPE;
     const int tix = threadIdx.x & (QA_BLOCK - 1), bix = blockIdx.x;
@@ -1164,8 +1256,10 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_post_physics_kernel(StepArgs a) {
     const int env = valid ? env_raw : N - 1, le = tix / LPE;
     const int64_t step = a.step;
     if (bix == 0 && tix < 16) p.episode_stats[16 * ((step + 1) & 1) + tix] = 0.f;
+    if (XR && bix == 0 && tix < 16) p.xr_stats[16 * ((step + 1) & 1) + tix] = 0.f;
     PostIn in;
     post_in_preload(in, p, env, leg, N);
+    post_in_preload_extra<XR>(in, p, env, leg, N);
     {
         const float *r = p.root + (int64_t)env * 13;
         in.st.pos = v3(r[0], r[1], r[2]); in.st.qx = r[3]; in.st.qy = r[4]; in.st.qz = r[5]; in.st.qw = r[6];
@@ -1187,7 +1281,7 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_post_physics_kernel(StepArgs a) {
         in.fric = p.friction[env];
     }
     TerrainView T = terrain_view(c, p, s_u);
-    post_physics_phase<PLANE, LPE>(c, p, a.mi, nullptr, in, T, s_tbl + leg * QA_LEG_TBL, s_u, s_u + EPB * S_ENV, tix, bix, env, leg, valid, true, le, step);
+    post_physics_phase<PLANE, LPE, 0, 0, XR>(c, p, a.mi, nullptr, in, T, s_tbl + leg * QA_LEG_TBL, s_u, s_u + EPB * S_ENV, tix, bix, env, leg, valid, true, le, step);
 }
 
 // ------------------------------------------------------------------ init / reset / simulate kernels
@@ -1242,8 +1336,12 @@ __global__ void qa_init_kernel(qa_config c, Ptrs p, BaseConst bc) {
 
 __global__ void __launch_bounds__(QA_BLOCK) qa_reset_all_kernel(qa_config c, Ptrs p, MocapIdx mi, int64_t step) {
     const int tid = blockIdx.x * QA_BLOCK + threadIdx.x, leg = threadIdx.x & 3, env = tid >> 2, N = c.num_envs;
-    if (blockIdx.x == 0 && threadIdx.x < 16) { p.episode_stats[16 * (step & 1) + threadIdx.x] = 0.f; }
+    if (blockIdx.x == 0 && threadIdx.x < 16) { p.episode_stats[16 * (step & 1) + threadIdx.x] = 0.f; if (p.xr_sums) p.xr_stats[16 * (step & 1) + threadIdx.x] = 0.f; }
     if (env >= N) return;
+    if (p.xr_sums) {          // reset_idx(all) for the extra reward terms' state
+        p.xr_air[(int64_t)env * 4 + leg] = 0.f;
+        for (int r = leg; r < QA_NUM_EXTRA_REWARDS; r += 4) p.xr_sums[(int64_t)r * N + env] = 0.f;
+    }
     EnvState st; float cmd[5], eps; int gait;
     reset_env(c, p, mi, env, leg, step, st, cmd, eps, gait);
     if (leg == 0) {
@@ -1387,6 +1485,12 @@ __global__ void __launch_bounds__(GAE_BLOCK) qa_gae_norm_kernel(float *advantage
 }
 
 // ------------------------------------------------------------------ host side
+static void clear_extra_rewards(Ptrs &p) {
+    p.xr_sums = nullptr; p.xr_air = nullptr; p.xr_stats = nullptr; p.xr_scan = nullptr; p.xr_scan_n = 0;
+    for (int i = 0; i < QA_NUM_EXTRA_REWARDS; ++i) p.xr_scale[i] = 0.f;
+    p.xr_target = 0.f; p.xr_max_force = 0.f; p.xr_dt = 0.f;
+}
+
 static void fill_ptrs(qa_sim *s) {
     char *a = s->arena; const Layout &L = s->L; Ptrs &p = s->p;
 #define FP(name, T_) p.name = (float *)(a + L.off[T_])
@@ -1410,6 +1514,7 @@ static void fill_ptrs(qa_sim *s) {
     p.mocap_clips = (double *)(a + L.off[QA_T_MOCAP_CLIPS]);
     p.ticket = (int32_t *)(a + L.off[QA_T_STEP_TICKET]);
     p.terrain_levels = nullptr; p.terrain_types = nullptr; p.terrain_origins = nullptr; p.terrain_rows = p.terrain_cols = 0; p.terrain_env_length = p.terrain_episode_s = 0.f;
+    clear_extra_rewards(p);
 }
 
 static void build_table(float *t) {
@@ -1511,22 +1616,27 @@ static void launch_env_step(qa_sim *s, const StepArgs &a, hipStream_t st) {
     // 0 = never (the one-wavefront kernels, A/B runs), 1 = always, unset = by launch size
     static const int helpers_switch = [] { const char *e = getenv("QA_ENV_HELPERS"); return e ? (atoi(e) != 0 ? 1 : 0) : QA_ENV_HELPERS_DEFAULT; }();
     const bool helpers = helpers_switch == 1 || (helpers_switch < 0 && blocks <= s->num_cus);
+    const bool xr = s->p.xr_sums != nullptr;           // qa_set_extra_rewards: the XR instantiations
+#define QA_LAUNCH_STEP(PLANE_, LEAN_, HELP_) do { \
+        if (xr) hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 1>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); \
+        else hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 0>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); } while (0)
     if (!hf && helpers) {
-        if (s->lean == 3) hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 0, 3, 1>), dim3(blocks), dim3(3 * QA_BLOCK), 0, st, a);
-        else if (s->lean == 1) hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 0, 1, 1>), dim3(blocks), dim3(3 * QA_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 0, 0, 1>), dim3(blocks), dim3(3 * QA_BLOCK), 0, st, a);
+        if (s->lean == 3) QA_LAUNCH_STEP(true, 3, 1);
+        else if (s->lean == 1) QA_LAUNCH_STEP(true, 1, 1);
+        else QA_LAUNCH_STEP(true, 0, 1);
         return;
     }
     if (s->lean == 3) {
-        if (hf) hipLaunchKernelGGL((qa_env_step_kernel<false, 4, 0, 3>), dim3(blocks), dim3(QA_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 0, 3>), dim3(blocks), dim3(QA_BLOCK), 0, st, a);
+        if (hf) QA_LAUNCH_STEP(false, 3, 0);
+        else QA_LAUNCH_STEP(true, 3, 0);
     } else if (s->lean == 1) {
-        if (hf) hipLaunchKernelGGL((qa_env_step_kernel<false, 4, 0, 1>), dim3(blocks), dim3(QA_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 0, 1>), dim3(blocks), dim3(QA_BLOCK), 0, st, a);
+        if (hf) QA_LAUNCH_STEP(false, 1, 0);
+        else QA_LAUNCH_STEP(true, 1, 0);
     } else {
-        if (hf) hipLaunchKernelGGL((qa_env_step_kernel<false, 4>), dim3(blocks), dim3(QA_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((qa_env_step_kernel<true, 4>), dim3(blocks), dim3(QA_BLOCK), 0, st, a);
+        if (hf) QA_LAUNCH_STEP(false, 0, 0);
+        else QA_LAUNCH_STEP(true, 0, 0);
     }
+#undef QA_LAUNCH_STEP
 }
 
 int qa_set_lean_exports(qa_sim *s, int32_t mask) {
@@ -1549,6 +1659,26 @@ int qa_set_terrain_curriculum(qa_sim *s, int64_t *terrain_levels, const int64_t 
     }
     p.terrain_levels = terrain_levels; p.terrain_types = terrain_types; p.terrain_origins = terrain_origins;
     p.terrain_rows = rows; p.terrain_cols = cols; p.terrain_env_length = env_length; p.terrain_episode_s = max_episode_length_s;
+    return QA_OK;
+}
+
+int qa_set_extra_rewards(qa_sim *s, const qa_extra_rewards *x) {
+    if (!s) return QA_E_ARG;
+    Ptrs &p = s->p;
+    if (!x) { clear_extra_rewards(p); return QA_OK; }
+    if (!x->extra_episode_sums || !x->feet_air_time || !x->extra_episode_stats) {
+        snprintf(g_err, sizeof(g_err), "qa_set_extra_rewards: extra_episode_sums, feet_air_time and extra_episode_stats are all needed (a NULL struct switches the terms off)"); return QA_E_ARG;
+    }
+    if (x->num_scan_points < 0 || x->num_scan_points > QA_MAX_SCAN_POINTS || (x->num_scan_points > 0) != (x->scan_offsets != nullptr)) {
+        snprintf(g_err, sizeof(g_err), "qa_set_extra_rewards: num_scan_points in [0, %d], scan_offsets non-NULL exactly when it is > 0", QA_MAX_SCAN_POINTS); return QA_E_ARG;
+    }
+    if (x->num_scan_points > 0 && s->cfg.terrain_type != 1) {
+        snprintf(g_err, sizeof(g_err), "qa_set_extra_rewards: a height scan needs a height field (terrain_type != 1)"); return QA_E_ARG;
+    }
+    p.xr_sums = x->extra_episode_sums; p.xr_air = x->feet_air_time; p.xr_stats = x->extra_episode_stats;
+    p.xr_scan = x->scan_offsets; p.xr_scan_n = x->num_scan_points;
+    for (int i = 0; i < QA_NUM_EXTRA_REWARDS; ++i) p.xr_scale[i] = x->scale_dt[i];
+    p.xr_target = x->base_height_target; p.xr_max_force = x->max_contact_force; p.xr_dt = x->step_dt;
     return QA_OK;
 }
 
@@ -1668,7 +1798,11 @@ int qa_debug_post_physics(qa_sim *s, int64_t global_step, void *stream) {
     if (!s) return QA_E_ARG;
     StepArgs a; a.c = s->cfg; a.p = s->p; a.mi = mocap_idx(s); a.actions = nullptr; a.delay = 0; a.step = global_step; a.step_ptr = nullptr; a.prof = nullptr;
     const int blocks = (s->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
-    if (s->cfg.terrain_type == 1) hipLaunchKernelGGL((qa_post_physics_kernel<false>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
+    const bool hf = s->cfg.terrain_type == 1;
+    if (s->p.xr_sums) {       // qa_set_extra_rewards: the XR instantiations
+        if (hf) hipLaunchKernelGGL((qa_post_physics_kernel<false, 1>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((qa_post_physics_kernel<true, 1>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
+    } else if (hf) hipLaunchKernelGGL((qa_post_physics_kernel<false>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((qa_post_physics_kernel<true>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return QA_OK;

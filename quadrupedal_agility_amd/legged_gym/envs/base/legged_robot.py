@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from quadrupedal_agility_amd import _capi
-from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import class_to_dict, make_qa_config
+from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import class_to_dict, make_extra_rewards, make_qa_config
 
 KEY_BODY_NAMES = ["FL_foot", "FR_foot", "RL_foot", "RR_foot"]
 
@@ -78,6 +78,7 @@ class LeggedRobot:
             self.sim.set_mocap(*self._mocap_table)
         self._init_buffers()
         self._install_terrain()
+        self._install_extra_rewards()          # before anything records a rollout: the handle keeps the buffers' pointers
         self._prepare_reward_function()
         self.init_done = True
 
@@ -115,9 +116,26 @@ class LeggedRobot:
             else:
                 self.reward_scales[key] *= self.dt
         self.reward_names = [n for n in self.reward_scales if n != "termination"]
-        assert self.reward_names == [n for n in _capi.REWARD_NAMES if n in self.reward_scales], self.reward_names
-        sums = self.sim.t["EPISODE_SUMS"]
-        self.episode_sums = {n: sums[_capi.REWARD_NAMES.index(n)] for n in self.reward_names}
+        assert self.reward_names == sorted(n for n in _capi.REWARD_NAMES + _capi.EXTRA_REWARD_NAMES if n in self.reward_names), self.reward_names
+        sums, extra = self.sim.t["EPISODE_SUMS"], (self.sim.extra_episode_sums if self._extra_rewards is not None else None)
+        # both sets in the reference's (alphabetical) order; `termination` has a sum but is no entry of reward_names (:936-946)
+        self.episode_sums = {n: sums[_capi.REWARD_NAMES.index(n)] if n in _capi.REWARD_NAMES else extra[_capi.EXTRA_REWARD_NAMES.index(n)]
+                             for n in self.reward_scales if n != "termination" or extra is not None}
+
+    def _install_extra_rewards(self):
+        """The ten terms of include/qa_sim_rewards.h with a non-zero scale run inside the fused step on buffers this env owns
+        (qa_set_extra_rewards).  `feet_air_time` is the live (N, 4) state when they are on."""
+        self._extra_rewards = make_extra_rewards(self.cfg, sim_dt=self.sim_params.dt)
+        self._extra_episode_means = None
+        if self._extra_rewards is None:
+            self.feet_air_time = torch.zeros(self.num_envs, 4, device=self.device)      # the reference's attribute; nothing advances it
+            return
+        if not hasattr(self.sim, "set_extra_rewards"):
+            names = [n for n, v in zip(_capi.EXTRA_REWARD_NAMES, self._extra_rewards.scale_dt) if v != 0]
+            raise NotImplementedError(f"reward terms {names} need the HIP engine (qa_set_extra_rewards); this backend has no twin of it")
+        self.sim.set_extra_rewards(self._extra_rewards)
+        self.feet_air_time = self.sim.feet_air_time
+        self._extra_episode_means = torch.zeros(_capi.NUM_EXTRA_REWARDS, device=self.device)
 
     # ------------------------------------------------------------------ buffers = views of the arena
     def _init_buffers(self):
@@ -354,7 +372,16 @@ class LeggedRobot:
             mean = st[:_capi.NUM_REWARDS] / torch.clamp(cnt, min=1.0) / self.max_episode_length_s
             self._episode_means.copy_(torch.where(cnt > 0, mean, self._episode_means))
             snap = self._episode_means.clone()
-        self.extras["episode"] = {"rew_" + n: snap[_capi.REWARD_NAMES.index(n)] for n in self.reward_names}
+        if self._extra_rewards is None:
+            self.extras["episode"] = {"rew_" + n: snap[_capi.REWARD_NAMES.index(n)] for n in self.reward_names}
+        else:
+            # the extra terms' bins (extra_episode_stats) are fed and laid out like EPISODE_STATS: the same launch reduces them
+            xstats, xsnap = self.sim.extra_episode_stats, torch.empty_like(self._extra_episode_means)
+            P = _capi._ptr
+            _capi.API.launch("episode_means", P(xstats), P(self._step_ctr) if self._step_ctr is not None else None, int(self.common_step_counter),
+                             _capi.NUM_EXTRA_REWARDS, float(self.max_episode_length_s), P(self._extra_episode_means), P(xsnap), on=xstats)
+            self.extras["episode"] = {"rew_" + n: snap[_capi.REWARD_NAMES.index(n)] if n in _capi.REWARD_NAMES else xsnap[_capi.EXTRA_REWARD_NAMES.index(n)]
+                                      for n in self.episode_sums}
         if self.cfg.terrain.curriculum:     # :235-236; the levels are the tensor the step just updated, the mean stays on the device
             self.extras["episode"]["terrain_level"] = torch.mean(self.terrain_levels.float())
         if self.cfg.env.send_timeouts:

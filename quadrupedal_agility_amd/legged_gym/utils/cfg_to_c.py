@@ -83,10 +83,10 @@ def make_qa_config(cfg, seed=1, sim_dt=None, terrain=None):
     c.s_key_pos, c.s_foot_contact = float(os_.key_pos), float(os_.foot_contact)
     c.s_lin_vel_dist, c.s_ang_vel_dist = float(os_.lin_vel_dist), float(os_.ang_vel_dist)
     scales = class_to_dict(cfg.rewards.scales)
-    known = set(_capi.REWARD_NAMES)
+    known = set(_capi.REWARD_NAMES) | set(_capi.EXTRA_REWARD_NAMES)       # the latter travel in make_extra_rewards' descriptor, not in qa_config
     for name, val in scales.items():
-        if val != 0 and name not in known and name != "termination":
-            raise NotImplementedError(f"reward term {name!r} has a non-zero scale but is not on the hot path")
+        if val != 0 and name not in known:
+            raise NotImplementedError(f"reward term {name!r} has a non-zero scale but is not on the hot path" + _NOT_ON_HOT_PATH.get(name, ""))
     for i, name in enumerate(_capi.REWARD_NAMES):
         c.reward_scale_dt[i] = float(scales.get(name, 0.0) * dt)     # legged_robot.py:927-932
     c.only_positive_rewards = int(bool(cfg.rewards.only_positive_rewards))
@@ -126,6 +126,39 @@ def make_qa_config(cfg, seed=1, sim_dt=None, terrain=None):
     c.env_id_offset = int(getattr(cfg.env, "env_id_offset", 0))
     c.num_envs_global = int(getattr(cfg.env, "num_envs_global", 0))
     return c
+
+
+_NOT_ON_HOT_PATH = {
+    "contact_force_balance": ": it reads a 100-step x 4-foot contact-force history per env, which the fused step does not keep",
+    "contact_balance": ": the reference has no _reward_contact_balance function either",
+}
+
+
+class ExtraRewards:
+    """What qa_set_extra_rewards (include/qa_sim_rewards.h) needs besides device buffers: `scale_dt` in _capi.EXTRA_REWARD_NAMES order,
+    the two targets, dt as the fp32 step the air time advances by, and the (n, 2) scan grid (None: measured heights are 0)."""
+
+    def __init__(self, scale_dt, base_height_target, max_contact_force, step_dt, scan_offsets):
+        self.scale_dt, self.base_height_target, self.max_contact_force = list(scale_dt), float(base_height_target), float(max_contact_force)
+        self.step_dt, self.scan_offsets = float(step_dt), scan_offsets
+
+
+def make_extra_rewards(cfg, sim_dt=None):
+    """The extension descriptor that goes next to make_qa_config's qa_config: the ten terms of _capi.EXTRA_REWARD_NAMES with a non-zero
+    scale, or None when none has one (the fused step then runs exactly as without the extension)."""
+    scales = class_to_dict(cfg.rewards.scales)
+    dt = cfg.control.decimation * (cfg.sim.dt if sim_dt is None else sim_dt)
+    scale_dt = [float(scales.get(name, 0.0) * dt) for name in _capi.EXTRA_REWARD_NAMES]          # legged_robot.py:927-932
+    if not any(scale_dt):
+        return None
+    scan = None
+    if cfg.terrain.mesh_type in ("heightfield", "trimesh") and cfg.terrain.measure_heights and scale_dt[_capi.EXTRA_REWARD_NAMES.index("base_height")] != 0:
+        # _init_height_points (:1174-1188): meshgrid(x, y) flattened x-major
+        x, y = np.asarray(cfg.terrain.measured_points_x, np.float32), np.asarray(cfg.terrain.measured_points_y, np.float32)
+        scan = np.stack([np.repeat(x, len(y)), np.tile(y, len(x))], axis=1).astype(np.float32)
+        if len(scan) > _capi.MAX_SCAN_POINTS:
+            raise NotImplementedError(f"base_height: {len(scan)} scan points, the fused step takes {_capi.MAX_SCAN_POINTS}")
+    return ExtraRewards(scale_dt, getattr(cfg.rewards, "base_height_target", 0.0), getattr(cfg.rewards, "max_contact_force", 0.0), dt, scan)
 
 
 def _gain(table):

@@ -96,6 +96,17 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             env_cfg.terrain.curriculum = True
         if getattr(args, "no_mocap_init", False):
             env_cfg.env.mocap_state_init = False
+        for item in getattr(args, "reward_scale", None) or []:
+            name, eq, value = item.partition("=")
+            if not hasattr(env_cfg.rewards.scales, name):
+                raise ValueError(f"--reward_scale {item}: rewards.scales has no term {name!r}")
+            try:
+                scale = float(value) if eq else None
+            except ValueError:
+                scale = None
+            if scale is None:
+                raise ValueError(f"--reward_scale {item}: expected NAME=VALUE with a number for VALUE")
+            setattr(env_cfg.rewards.scales, name, scale)
     if cfg_train is not None:
         if getattr(args, "seed", None) is not None:
             cfg_train.seed = args.seed
@@ -140,6 +151,8 @@ def get_args(argv=None):
     p.add_argument("--physics_engine", default="qa")
     p.add_argument("--terrain", type=str, default=None, help="override terrain.mesh_type: plane | heightfield | trimesh")
     p.add_argument("--terrain_curriculum", action="store_true", help="terrain.curriculum = True: resetting envs move between the course's difficulty rows (heightfield | trimesh)")
+    p.add_argument("--reward_scale", action="append", default=[], metavar="NAME=VALUE",
+                   help="rewards.scales.NAME = VALUE (repeatable), e.g. lin_vel_z=-2.0 feet_air_time=1.0: any term the fused step computes")
     p.add_argument("--no_amp", action="store_true", help="disable the discriminator (BASELINE config 2)")
     p.add_argument("--no_mocap_init", action="store_true", help="reset from the default pose instead of mocap frames")
     p.add_argument("--log_root", type=str, default="default")

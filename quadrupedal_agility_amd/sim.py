@@ -78,6 +78,33 @@ class QaSim:
                       float(env_length), float(max_episode_length_s))
         self._curriculum = (terrain_levels, terrain_types, terrain_origins)
 
+    def set_extra_rewards(self, extra):
+        """qa_set_extra_rewards (include/qa_sim_rewards.h): `extra` is cfg_to_c.make_extra_rewards' descriptor; None switches the terms off.
+        Allocates the caller-owned buffers -- `extra_episode_sums` (10, N), `feet_air_time` (N, 4), `extra_episode_stats` (2, 16) -- and keeps
+        them alive; the handle keeps their POINTERS, so call this before a rollout is recorded."""
+        if extra is None:
+            self.api.call("set_extra_rewards", self.h, None)
+            self.extra_rewards = None
+            self.extra_episode_sums = self.feet_air_time = self.extra_episode_stats = self._scan_offsets = None
+            return
+        n, dev = self.cfg.num_envs, self.device
+        self.extra_episode_sums = torch.zeros(_capi.NUM_EXTRA_REWARDS, n, device=dev)
+        self.feet_air_time = torch.zeros(n, 4, device=dev)
+        self.extra_episode_stats = torch.zeros(2, 16, device=dev)
+        self._scan_offsets = None
+        if extra.scan_offsets is not None and len(extra.scan_offsets):
+            self._scan_offsets = torch.as_tensor(extra.scan_offsets, dtype=torch.float32).reshape(-1, 2).contiguous().to(dev)
+        x = _capi.QaExtraRewards()
+        for i, v in enumerate(extra.scale_dt):
+            x.scale_dt[i] = float(v)
+        x.base_height_target, x.max_contact_force, x.step_dt = extra.base_height_target, extra.max_contact_force, extra.step_dt
+        x.num_scan_points = 0 if self._scan_offsets is None else int(self._scan_offsets.shape[0])
+        x.scan_offsets = None if self._scan_offsets is None else self._scan_offsets.data_ptr()
+        x.extra_episode_sums, x.feet_air_time, x.extra_episode_stats = (self.extra_episode_sums.data_ptr(), self.feet_air_time.data_ptr(),
+                                                                         self.extra_episode_stats.data_ptr())
+        self.api.call("set_extra_rewards", self.h, C.byref(x))
+        self.extra_rewards = extra
+
     def step_dev(self, actions, delay, step_counter):
         """qa_env_step_dev: the step counter lives in device memory (graph-replayable)."""
         assert actions.is_cuda and actions.dtype == torch.float32 and actions.is_contiguous()
