@@ -277,6 +277,10 @@ struct ContactOut {
     V3 extra_f[QA_EXTRA_SLOTS];     // world-frame force on the slot's contact
     int extra_body[QA_EXTRA_SLOTS]; // body id the slot's contact is on (-1 none)
     V3 self_f;                      // world-frame force of this leg's self-collisions (both partners), on its calf
+    // SCH instantiations only (calf against the neighbouring hip): the row's impulse of this substep (0 while the pair is apart) and the world-frame
+    // direction of its force on THIS leg's body -- the calf of a front leg, the hip of a rear leg.  The kernels turn them into a force behind
+    // phys_substep: the block below that reports the other forces stays the same code with and without the rows
+    float sh_lam; V3 sh_dir;
 };
 
 // Self-collision (the reference enables it: bbc/.../go2_locomotion_config.py:72, tsc/.../go2_agility_config.py:43 `self_collisions = 0`): the
@@ -288,6 +292,10 @@ struct ContactOut {
 #define QA_CALF_RADIUS 0.013f
 #define QA_FOOT_RADIUS 0.022f
 #define QA_PRIV_SELF 140                 // 2 pair rows x 20 floats
+// The calf of a front leg against the hip of the rear leg of its side (SCH instantiations, include/qa_sim_selfcol.h): the one ordered relation
+// that can come within the contact offset under the joint limits.  Same algebra as above, with chain depth 3 on the calf's
+// side and 1 on the hip's (only joint 0 moves the hip cylinder).  Geometry: qa_selfcol.h, shared with the host twin.
+#include "qa_selfcol.h"
 // closest points of segments A0 + s (A1 - A0), B0 + t (B1 - B0), s, t in [0, 1] (Ericson, Real-Time Collision Detection 5.1.9)
 QA_DEV void segment_closest(V3 A0, V3 A1, V3 B0, V3 B1, float &s, float &t) {
     const V3 d1 = A1 - A0, d2 = B1 - B0, r = A0 - B0;
@@ -390,6 +398,8 @@ __device__ long long *g_subprof = nullptr;
 #define QA_PRIV_EXTRA 0                  // 2 slots x 3 rows x 20 floats: jh6 jl3 bj6 lj3 dinv bias
 #define QA_PRIV_STEP 120                 // env-step persistents parked between substeps: act3 sp3 sd3 binert10
 #define QA_PRIV_FLOATS 180
+#define QA_PRIV_HIPS 180                 // SCH instantiations: 1 calf-hip row x 20 floats behind the records above ...
+#define QA_PRIV_FLOATS_SCH 204           // ... and a lane stride that is again an odd number of 16-byte records (51)
 struct LRow { float *p; };               // row view in LDS
 QA_DEV float &lr(float *priv, int k) { return priv[k * QA_PRIV_STRIDE]; }
 
@@ -523,7 +533,17 @@ QA_DEV void prow_load(const float *rec, PRow &r) {
     r.j[0] = f2{a.x, a.y}; r.j[1] = f2{a.z, a.w}; r.j[2] = f2{b.x, b.y}; r.j[3] = f2{b.z, b.w}; r.j[4] = f2{c.x, c.y};
     r.m[0] = f2{c.z, c.w}; r.m[1] = f2{d.x, d.y}; r.m[2] = f2{d.z, d.w}; r.m[3] = f2{e.x, e.y}; r.m[4] = f2{e.z, 0.f}; r.dinv = e.w;
 }
-QA_DEV float *priv_of(float *s_priv, int tix) { return s_priv + tix * QA_PRIV_FLOATS; }
+template <int SCH = 0>
+QA_DEV float *priv_of(float *s_priv, int tix) { return s_priv + tix * (SCH ? QA_PRIV_FLOATS_SCH : QA_PRIV_FLOATS); }
+// the reported force of the calf-hip row (SCH): +n on the front leg's calf (body 5 + 4 leg), -n on the rear leg's hip (body 3 + 4 leg)
+QA_DEV void sch_forces(const ContactOut &co, float dt, int leg, V3 &hip_f, V3 &calf_f) {
+    const V3 f = (co.sh_lam * (1.0f / dt)) * co.sh_dir;
+    const bool calf = (leg & 2) == 0;
+    // selects, not "+ 0": -0.0 + 0.0 is +0.0, and with no pair in reach the exported forces are to keep every bit
+    const V3 h = hip_f + f, c = calf_f + f;
+    hip_f = calf ? hip_f : h;
+    calf_f = calf ? c : calf_f;
+}
 // env-step persistents parked between substeps (act3 sp3 sd3 binert10) as five 16-byte records at QA_PRIV_STEP
 QA_DEV void priv_park(float *priv, const float *act, const float *sp, const float *sd, const float *bi) {
     f4 *q = reinterpret_cast<f4 *>(priv + QA_PRIV_STEP);
@@ -589,7 +609,21 @@ QA_DEV void mail_get_solve(const f4 *m, PSolve &S) {
     S.L2[0] = l.x; S.L2[1] = l.y; S.L2[2] = l.z;
 }
 
-template <bool PLANE, int ROLE = 0>
+// idt (lp vp + l1 v1 + l2 v2), the world-frame force of a contact on sloped ground, with its multiply-adds SPELLED OUT: the product lp vp rounded, then
+// one fused multiply-add per remaining term, in this order.  -ffp-contract=fast leaves the fusing of `idt * ((lam_n * n) + (lam_t1 * t1) + (lam_t2 * t2))`
+// to the compiler, and it chooses per instantiation: read off the listings, every SCH = 0 kernel rounds lam_n n of the FOOT force and lam_t1 t1 of an
+// extra slot's force, while the SCH = 1 kernels rounded lam_t1 t1 of the foot force -- the reported foot forces then differed in the last bit with no
+// calf-hip pair anywhere near contact.  Only the SCH = 1 instantiations call this, with the terms in the SCH = 0 kernels' order: with the feature
+// switched on and no pair in reach, every arena tensor stays bit-identical.
+QA_DEV V3 sloped_contact_force(float lp, V3 vp, float l1, V3 v1, float l2, V3 v2, float idt) {
+#pragma clang fp contract(off)
+    const float x = __builtin_fmaf(l2, v2.x, __builtin_fmaf(l1, v1.x, lp * vp.x));
+    const float y = __builtin_fmaf(l2, v2.y, __builtin_fmaf(l1, v1.y, lp * vp.y));
+    const float z = __builtin_fmaf(l2, v2.z, __builtin_fmaf(l1, v1.z, lp * vp.z));
+    return v3(idt * x, idt * y, idt * z);
+}
+
+template <bool PLANE, int ROLE = 0, int SCH = 0>
 QA_DEV void phys_substep(EnvState &st, const float *tbl, const float *btbl, const float *binert, const float tau[3],
                          float mu, int leg, const PhysParams &P, ContactOut &co, float *priv, float fimp[3], const TerrainView &T, f4 *mail = nullptr) {
     static_assert(ROLE == 0 || PLANE, "helper wavefronts: plane kernels only (the height-field candidates carry six more values per contact)");
@@ -936,6 +970,59 @@ QA_DEV void phys_substep(EnvState &st, const float *tbl, const float *btbl, cons
             }
         }
     }
+    // ---- calf against the neighbouring hip (SCH): the pair is (front leg, rear leg of the same side) = lane ^ 2; the front lane holds the calf,
+    // the rear lane the hip.  Both evaluate qa_sc_calf_hip on the SAME four points (calf first), so they agree bit for bit on gap and normal;
+    // the row is built and swept exactly like a front / rear calf-calf row.  Rare: scalar arithmetic, the row in the lane's LDS record.
+    bool sh_on = false, any_sh = false;
+    const bool sh_calf = (leg & 2) == 0;
+    float sh_lam = 0.f;
+    V3 sh_nw = v3(0.f, 0.f, 0.f);
+    if constexpr (SCH != 0) {
+        const float org[3] = {o[0].x, o[0].y, o[0].z};
+        float h0[3], h1[3];
+        qa_sc_hip_segment(org, c1, s1, (leg & 1) ? -1.f : 1.f, h0, h1);
+        // a lane sends what its side of the pair contributes and receives the other side's: 6 quad_perm moves
+        const float snd[6] = {sh_calf ? o[2].x : h0[0], sh_calf ? o[2].y : h0[1], sh_calf ? o[2].z : h0[2],
+                              sh_calf ? foot_p.x : h1[0], sh_calf ? foot_p.y : h1[1], sh_calf ? foot_p.z : h1[2]};
+        float cs[6], hs[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { const float rcv = dpp_f<0x4E>(snd[i]); cs[i] = sh_calf ? snd[i] : rcv; hs[i] = sh_calf ? rcv : snd[i]; }
+        qa_sc_contact ct;
+        qa_sc_calf_hip(cs, cs + 3, hs, hs + 3, &ct);
+        sh_on = ct.gap < P.contact_offset;
+        any_sh = __any(sh_on);
+        const float sg = sh_calf ? 1.f : -1.f;
+        sh_nw = v3(sg * ct.n[0], sg * ct.n[1], sg * ct.n[2]);       // base frame: direction of the force on THIS leg's body
+        co.sh_dir = mul(R, sh_nw);
+        if (any_sh) {
+            Row r;
+            const V3 pm = sh_calf ? v3(ct.pc[0], ct.pc[1], ct.pc[2]) : v3(ct.ph[0], ct.ph[1], ct.ph[2]);
+            r.jl[0] = dot(sh_nw, cross(ax[0], pm - o[0]));
+            // the hip cylinder rides on the hip link: joints 1 and 2 of its leg do not move it
+            r.jl[1] = sh_calf ? dot(sh_nw, cross(ax[1], pm - o[1])) : 0.f;
+            r.jl[2] = sh_calf ? dot(sh_nw, cross(ax[2], pm - o[2])) : 0.f;
+            float h[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) h[i] = G[0 * 6 + i] * r.jl[0] + G[1 * 6 + i] * r.jl[1] + G[2 * 6 + i] * r.jl[2];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) r.jh[i] = h[i] + dpp_f<0x4E>(h[i]);
+            sym6_mul(Binv, r.jh, r.bj);
+            r.lj[0] = Linv[0] * r.jl[0] + Linv[1] * r.jl[1] + Linv[2] * r.jl[2];
+            r.lj[1] = Linv[1] * r.jl[0] + Linv[3] * r.jl[1] + Linv[4] * r.jl[2];
+            r.lj[2] = Linv[2] * r.jl[0] + Linv[4] * r.jl[1] + Linv[5] * r.jl[2];
+            const float dleg = r.jl[0] * r.lj[0] + r.jl[1] * r.lj[1] + r.jl[2] * r.lj[2];
+            float d = dleg + dpp_f<0x4E>(dleg);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) d = fmaf(r.jh[i], r.bj[i], d);
+            const float g = ct.gap / dt;
+            PRow pr_;
+            pr_.j[0] = f2{r.jh[0], r.jh[1]}; pr_.j[1] = f2{r.jh[2], r.jh[3]}; pr_.j[2] = f2{r.jh[4], r.jh[5]}; pr_.j[3] = f2{r.jl[0], r.jl[1]};
+            pr_.j[4] = f2{r.jl[2], ct.gap >= 0.f ? g : fmaxf(g, -P.max_depen)};
+            pr_.m[0] = f2{r.bj[0], r.bj[1]}; pr_.m[1] = f2{r.bj[2], r.bj[3]}; pr_.m[2] = f2{r.bj[4], r.bj[5]}; pr_.m[3] = f2{r.lj[0], r.lj[1]}; pr_.m[4] = f2{r.lj[2], 0.f};
+            pr_.dinv = 1.0f / (d + QA_CFM);
+            prow_store(priv + QA_PRIV_HIPS, pr_);
+        }
+    }
     // joint limits: at most one stop per joint can be within the margin.  jl = sgn e_k  =>  jh = sgn G[k,:], lj = sgn Linv[:,k]
     float lim_sgn[3], lim_bias[3], lim_lam[3], lim_dinv[3];   // registers: these rows run in most waves
     f2 lim_m[3][3];
@@ -1086,6 +1173,25 @@ QA_DEV void phys_substep(EnvState &st, const float *tbl, const float *btbl, cons
                 x[0] += f2{quad_sum(db0.x), quad_sum(db0.y)}; x[1] += f2{quad_sum(db1.x), quad_sum(db1.y)}; x[2] += f2{quad_sum(db2.x), quad_sum(db2.y)};
             }
         }
+        // calf-hip pairs (SCH): the two front / rear pairs from the same base velocity, the front lane of a pair reporting its base-velocity change;
+        // the same wave-uniform vote, the same own + partner ordering and the same dl = 0 for a lane whose pair is apart as above
+        if constexpr (SCH != 0) {
+            if (any_sh) {
+                PRow r; prow_load(priv + QA_PRIV_HIPS, r);
+                const float tl = r.j[3].x * x[3].x + r.j[3].y * x[3].y + r.j[4].x * x[4].x;
+                const float tls = tl + dpp_f<0x4E>(tl);
+                float res = r.j[4].y + tls;
+                res = fmaf(r.j[0].x, x[0].x, res); res = fmaf(r.j[0].y, x[0].y, res); res = fmaf(r.j[1].x, x[1].x, res);
+                res = fmaf(r.j[1].y, x[1].y, res); res = fmaf(r.j[2].x, x[2].x, res); res = fmaf(r.j[2].y, x[2].y, res);
+                const float lam = sh_on ? fmaxf(sh_lam - res * r.dinv, 0.f) : sh_lam, dl = lam - sh_lam;
+                sh_lam = lam;
+                x[3] = pfma(r.m[3], f2s(dl), x[3]);
+                x[4].x = fmaf(r.m[4].x, dl, x[4].x);
+                const float dlb = sh_calf ? dl : 0.f;
+                const f2 db0 = r.m[0] * f2s(dlb), db1 = r.m[1] * f2s(dlb), db2 = r.m[2] * f2s(dlb);
+                x[0] += f2{quad_sum(db0.x), quad_sum(db0.y)}; x[1] += f2{quad_sum(db1.x), quad_sum(db1.y)}; x[2] += f2{quad_sum(db2.x), quad_sum(db2.y)};
+            }
+        }
     }
     ub[0] = x[0].x; ub[1] = x[0].y; ub[2] = x[1].x; ub[3] = x[1].y; ub[4] = x[2].x; ub[5] = x[2].y;
     w[0] = x[3].x; w[1] = x[3].y; w[2] = x[4].x;
@@ -1126,11 +1232,13 @@ QA_DEV void phys_substep(EnvState &st, const float *tbl, const float *btbl, cons
     // ---- contact forces, world frame (plane: t1, t2, n are world x, y, z)
     float idt = 1.0f / dt;
     if (PLANE) co.foot_f = foot_on ? v3(rf[1].lam * idt, rf[2].lam * idt, rf[0].lam * idt) : v3(0, 0, 0);
+    else if constexpr (SCH != 0) co.foot_f = foot_on ? sloped_contact_force(rf[0].lam, foot_n, rf[1].lam, ft1_w, rf[2].lam, ft2_w, idt) : v3(0, 0, 0);
     else co.foot_f = foot_on ? idt * ((rf[0].lam * foot_n) + (rf[1].lam * ft1_w) + (rf[2].lam * ft2_w)) : v3(0, 0, 0);    // lam_n n + lam_t1 t1 + lam_t2 t2, world frame
 #pragma unroll
     for (int sl = 0; sl < QA_EXTRA_SLOTS; ++sl) {
         const bool on = any_extra[sl] && extra_on[sl];
         if (PLANE) co.extra_f[sl] = on ? v3(re_lam[sl][1] * idt, re_lam[sl][2] * idt, re_lam[sl][0] * idt) : v3(0, 0, 0);
+        else if constexpr (SCH != 0) { V3 a, b; tangent_basis(ex_n[sl], a, b); co.extra_f[sl] = on ? sloped_contact_force(re_lam[sl][1], a, re_lam[sl][0], ex_n[sl], re_lam[sl][2], b, idt) : v3(0, 0, 0); }
         else { V3 a, b; tangent_basis(ex_n[sl], a, b); co.extra_f[sl] = on ? idt * ((re_lam[sl][0] * ex_n[sl]) + (re_lam[sl][1] * a) + (re_lam[sl][2] * b)) : v3(0, 0, 0); }
         co.extra_body[sl] = on ? ex_body[sl] : -1;
     }
@@ -1139,6 +1247,7 @@ QA_DEV void phys_substep(EnvState &st, const float *tbl, const float *btbl, cons
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) if (any_sc[pr] && sc_on[pr]) co.self_f = co.self_f + (sc_lam[pr] * idt) * mul(R, sc_nw[pr]);
     }
+    if constexpr (SCH != 0) co.sh_lam = sh_lam;          // only ever changed under sh_on: 0 for a lane whose pair is apart
     // ---- what the contacts do to the articulated obstacles' joints: generalised force -f_n ca, summed over the quad, kept per env in LDS
     if (!PLANE && T.ob_acc) {
         float ga[QA_OBST_PER_ENV];

@@ -19,6 +19,7 @@
 #include "../../include/qa_sim.h"
 #include "../../include/qa_sim_curriculum.h"
 #include "../../include/qa_sim_rewards.h"
+#include "../../include/qa_sim_selfcol.h"
 #include "qa_go2_model.h"
 #include "qa_physics.h"
 #include "qa_rewards.h"
@@ -28,6 +29,15 @@
 
 static_assert(QA_NUM_LEG_PTS == QA_LEG_PTS && QA_NUM_BASE_PTS == QA_BASE_PTS, "model/table mismatch");
 
+// This file is compiled twice.  On its own it is the library's env engine with the kernels as they always were.  Included by qa_sim_selfcol.hip
+// with QA_SIM_SCH_TU defined it contributes only the kernel templates, which that file instantiates with SCH = 1 (qa_set_self_collision_hips) behind
+// the qa_sch_* launchers declared below: instantiating them HERE, next to the others, changed the code the compiler generated for the existing
+// kernels (same instructions, another schedule and register assignment), and those are to stay exactly as they are.  A code object has its own
+// constant memory, so the second translation unit keeps its own copy of the table (qa_sch_upload_table).
+#ifdef QA_SIM_SCH_TU
+#define c_tbl c_tbl_sch
+#define g_subprof g_subprof_sch
+#endif
 __constant__ float c_tbl[QA_TBL_FLOATS];
 
 // ------------------------------------------------------------------ arena layout (ABI: enum order, 256 B aligned)
@@ -114,6 +124,7 @@ struct qa_sim {
     long long *prof = nullptr;
     int lanes = 4;                 // lanes per env of the step / simulate kernels (one quad: lane & 3 = leg)
     int lean = 0;                  // qa_set_lean_exports
+    int sc_hips = 0;               // qa_set_self_collision_hips: the SCH instantiations of the step / simulate kernels
     int num_cus = 256;             // compute units of the device the arena lives on (launch_env_step: helper wavefronts by launch size)
     qa_config cfg;
     Layout L;
@@ -125,7 +136,11 @@ struct qa_sim {
 
 struct MocapIdx { int32_t on; };      // clips uploaded; the per-gait clip ranges live in column 5 of QA_T_MOCAP_CLIPS
 
+#ifdef QA_SIM_SCH_TU
+extern thread_local char qa_err_buf[512];
+#else
 thread_local char qa_err_buf[512] = "";      // shared with qa_learner.hip
+#endif
 #define g_err qa_err_buf
 static int fail_hip(hipError_t e, const char *what) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
@@ -907,7 +922,9 @@ QA_DEV void shift_history_store(const Ptrs &p, int bix, int lane, int N, float (
 // whose own post_physics_step (goals, termination, rewards, reset, three observation rows) are separate kernels (qa_tsc_*).
 // HELP = 1 (plane kernels): two helper wavefronts per workgroup take the bias forces and the contact candidates of every substep off the env's own
 // wavefront (phys_substep ROLE 1 / 2 / 3, qa_physics.h) -- three of a CU's four SIMDs idle otherwise at one wavefront per CU.
-template <bool PLANE, int LPE, int MODE = 0, int LEAN = 0, int HELP = 0, int XR = 0>
+// SCH = 1 (qa_set_self_collision_hips): the substeps also collide each front calf with the rear hip of its side; one more 16-byte-aligned row record
+// per lane in LDS (46 -> 52 KB of private slots per workgroup).  The SCH = 0 instantiations are the kernels as they were.
+template <bool PLANE, int LPE, int MODE = 0, int LEAN = 0, int HELP = 0, int XR = 0, int SCH = 0>
 __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(StepArgs a) {
     static_assert(XR == 0 || MODE == 0, "the extra reward terms belong to the behaviour-level post-physics phase");
     static_assert(LEAN == 0 || MODE == 0, "the task-level tree reads every tensor the physics step exports");
@@ -925,12 +942,13 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
     // holds -- 160 KB per CU -- and with it the throughput once there are more workgroups than CUs):
     //   physics phase:      per-lane private slots | terrain windows (height field only)
     //   observation phase:  per-env staging | OBS_GROUP assembled observation rows
-    constexpr int U_PHYS = QA_PRIV_FLOATS * QA_PRIV_STRIDE + (PLANE ? 0 : EPB * QA_PATCH * QA_PATCH + EPB * QA_OB_LDS);
+    constexpr int PRIV_FLOATS = SCH ? QA_PRIV_FLOATS_SCH : QA_PRIV_FLOATS;
+    constexpr int U_PHYS = PRIV_FLOATS * QA_PRIV_STRIDE + (PLANE ? 0 : EPB * QA_PATCH * QA_PATCH + EPB * QA_OB_LDS);
     constexpr int U_OBS = EPB * S_ENV + OBS_GROUP * S_ROW;
     constexpr int U_ALL = ((U_PHYS > U_OBS ? U_PHYS : U_OBS) + 3) & ~3;
     __shared__ __attribute__((aligned(16))) float s_u_all[WPB * U_ALL];
     float *s_u = s_u_all;
-    float *s_priv = s_u, *s_patch = s_u + QA_PRIV_FLOATS * QA_PRIV_STRIDE;
+    float *s_priv = s_u, *s_patch = s_u + PRIV_FLOATS * QA_PRIV_STRIDE;
     float *s_stage = s_u, *s_rows = s_u + EPB * S_ENV;
     static_assert((EPB * S_ENV) % 4 == 0, "row buffer must stay 16-byte aligned");
     long long *const qa_prof = a.prof;
@@ -951,7 +969,7 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
         PhysParams P; P.dt = c.sim_dt; P.gz = c.gravity_z; P.contact_offset = c.contact_offset; P.max_depen = c.max_depenetration_velocity;
         P.ground_friction = c.ground_friction; P.iters = c.solver_iterations; P.slots = c.contact_slots == 1 ? 1 : 2; P.self_collision = c.self_collision;
         TerrainView T = terrain_view(c, a.p, s_u);
-        float *priv = priv_of(s_u, tix);
+        float *priv = priv_of<SCH>(s_u, tix);
         EnvState st; ContactOut co;
         float fimp[3] = {0.f, 0.f, 0.f}, tau[3] = {0.f, 0.f, 0.f};
         // The history shift of the observation rows (513 floats per env read and written, 3/4 of the launch's bytes) is pure data movement: the bias
@@ -968,8 +986,8 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
             mail_get_state(mail, st);
             float bi[10], pa[3], psp[3], psd[3];
             priv_unpark(priv, pa, psp, psd, bi);
-            if (role == 1) phys_substep<PLANE, HELP ? 2 : 0>(st, tbl, btbl, bi, tau, 0.f, leg, P, co, priv, fimp, T, mail);
-            else phys_substep<PLANE, HELP ? 3 : 0>(st, tbl, btbl, bi, tau, 0.f, leg, P, co, priv, fimp, T, mail);
+            if (role == 1) phys_substep<PLANE, HELP ? 2 : 0, SCH>(st, tbl, btbl, bi, tau, 0.f, leg, P, co, priv, fimp, T, mail);
+            else phys_substep<PLANE, HELP ? 3 : 0, SCH>(st, tbl, btbl, bi, tau, 0.f, leg, P, co, priv, fimp, T, mail);
             // the history stores go out behind the second-to-last substep's last barrier, while the env's wavefront runs that substep's sweeps
             // (~10 k cycles in which this helper has nothing to do): 17 MB of writes from 256 CUs need ~5 us to be acknowledged, and the env's
             // wavefront must not find itself waiting for that at the workgroup's last barrier
@@ -1103,7 +1121,7 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
     // ---- decimation x (PD torque -> physics)   legged_robot.py:101-106, :547-579
     // per-step constants are parked in per-lane LDS slots between substeps so that they do not hold VGPRs
     // through the substep (the substep alone needs ~340 registers)
-    float *priv = priv_of(s_priv, tix);
+    float *priv = priv_of<SCH>(s_priv, tix);
     priv_park(priv, act, sp, sd, binert);
     float tau[3], tau_org[3];
     ContactOut co;
@@ -1142,7 +1160,7 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
             float lim = tbl[T_EFFORT + k];
             tau[k] = clampf(t, -lim, lim);
         }
-        phys_substep<PLANE, HELP ? 1 : 0>(st, tbl, btbl, bi, tau, mu, leg, P, co, priv, fimp, T, mail);
+        phys_substep<PLANE, HELP ? 1 : 0, SCH>(st, tbl, btbl, bi, tau, mu, leg, P, co, priv, fimp, T, mail);
     }
     { float bi_[10]; priv_unpark(priv, act, sp, sd, bi_); }
     st.pos.x += anc_x; st.pos.y += anc_y;               // back to world coordinates: ONE rounding per step, like the oracle's double -> float store
@@ -1183,6 +1201,7 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
         hl_f = v3(xsum<LPE>(e2.x), xsum<LPE>(e2.y), xsum<LPE>(e2.z));
     }
     V3 hip_f = on_body(myb), thigh_f = on_body(myb + 1), calf_f = on_body(myb + 2) + co.self_f;
+    if constexpr (SCH != 0) sch_forces(co, c.sim_dt, leg, hip_f, calf_f);          // a neighbour's calf on this leg's hip: check_termination sees it below
     if (valid && !(LEAN & 1)) {
         float *cf = p.cforce + (int64_t)env * 57, *rb = p.rbpos + (int64_t)env * 57;
         float *m = cf + 3 * myb;
@@ -1290,6 +1309,7 @@ __device__ __forceinline__ float normal_from(float u1, float u2) {
     return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
 
+#ifndef QA_SIM_SCH_TU
 struct BaseConst { float m, com[3], I[6]; };
 
 __global__ void qa_init_kernel(qa_config c, Ptrs p, BaseConst bc) {
@@ -1364,11 +1384,13 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_reset_all_kernel(qa_config c, Ptr
     for (int i = leg; i < 570; i += 4) p.obs[(int64_t)env * QA_NUM_OBS + 90 + i] = 0.f;
 }
 
-template <bool PLANE, int LPE>
+#endif   // QA_SIM_SCH_TU
+
+template <bool PLANE, int LPE, int SCH = 0>
 __global__ void __launch_bounds__(QA_BLOCK) qa_simulate_kernel(qa_config c, Ptrs p, const float *torques, const uint8_t *cond) {
     if (cond && *cond == 0) return;               // qa_simulate_if: the whole launch is a no-op (uniform over the grid)
     __shared__ float s_tbl[QA_TBL_FLOATS];
-    __shared__ __attribute__((aligned(16))) float s_priv[QA_PRIV_FLOATS * QA_PRIV_STRIDE];
+    __shared__ __attribute__((aligned(16))) float s_priv[(SCH ? QA_PRIV_FLOATS_SCH : QA_PRIV_FLOATS) * QA_PRIV_STRIDE];
     __shared__ float s_patch[PLANE ? 1 : ENVS_PER_BLOCK * QA_PATCH * QA_PATCH];
     __shared__ float s_ob[PLANE ? 1 : ENVS_PER_BLOCK * QA_OB_LDS];
     static_assert(LPE == 4, "one quad per env");
@@ -1403,7 +1425,7 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_simulate_kernel(qa_config c, Ptrs
     }
     const float anc_x = st.pos.x, anc_y = st.pos.y;     // env-local horizontal coordinates inside the substep (TerrainView)
     st.pos.x = 0.f; st.pos.y = 0.f;
-    phys_substep<PLANE>(st, tbl, btbl, binert, tau, 0.5f * (p.friction[env] + c.ground_friction), leg, P, co, priv_of(s_priv, threadIdx.x), fimp, T);
+    phys_substep<PLANE, 0, SCH>(st, tbl, btbl, binert, tau, 0.5f * (p.friction[env] + c.ground_friction), leg, P, co, priv_of<SCH>(s_priv, threadIdx.x), fimp, T);
     st.pos.x += anc_x; st.pos.y += anc_y;
     V3 org[4]; leg_origins(st.q, tbl, org);
     M3 R = quat_to_mat(st.qx, st.qy, st.qz, st.qw);
@@ -1421,6 +1443,7 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_simulate_kernel(qa_config c, Ptrs
     for (int k = 0; k < 3; ++k) {
         V3 f = on_body(myb + k);
         if (k == 2) f = f + co.self_f;
+        if constexpr (SCH != 0) { V3 hf_ = z, cf_ = z; sch_forces(co, c.sim_dt, leg, hf_, cf_); if (k == 0) f = f + hf_; if (k == 2) f = f + cf_; }
         cf[3 * (myb + k)] = f.x; cf[3 * (myb + k) + 1] = f.y; cf[3 * (myb + k) + 2] = f.z;
         V3 w = mul(R, org[k]) + st.pos; rb[3 * (myb + k)] = w.x; rb[3 * (myb + k) + 1] = w.y; rb[3 * (myb + k) + 2] = w.z;
     }
@@ -1439,6 +1462,13 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_simulate_kernel(qa_config c, Ptrs
     }
 }
 
+// the launchers of the SCH instantiations (defined in the translation unit of qa_sim_selfcol.hip, see the top of this file)
+int qa_sch_upload_table(const float *tbl, size_t bytes);
+void qa_sch_launch_env_step(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a);
+void qa_sch_launch_physics_step(bool hf, int blocks, hipStream_t st, const StepArgs &a);
+void qa_sch_launch_simulate(bool hf, int blocks, hipStream_t st, const qa_config &c, const Ptrs &p, const float *torques, const uint8_t *cond);
+
+#ifndef QA_SIM_SCH_TU
 // ------------------------------------------------------------------ fused GAE (rollout_storage.py:97-111)
 // pass 1: one lane per env, reverse scan over T (coalesced across envs); per-block partial sums in double.
 #define GAE_BLOCK 256
@@ -1572,6 +1602,7 @@ int qa_create(const qa_config *cfg, void *arena, int64_t arena_bytes, void *stre
     { int dev = 0, cus = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) s->num_cus = cus; }
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_tbl), tbl, sizeof(tbl));
     if (e != hipSuccess) { delete s; return fail_hip(e, "hipMemcpyToSymbol(c_tbl)"); }
+    if (qa_sch_upload_table(tbl, sizeof(tbl)) != QA_OK) { delete s; return QA_E_DEVICE; }
     e = hipMemsetAsync(arena, 0, (size_t)s->L.total, st);
     if (e != hipSuccess) { delete s; return fail_hip(e, "hipMemsetAsync(arena)"); }
     if (cfg->terrain_type == 1 && cfg->hf_ceiling) {     // "no overhang anywhere" until the caller writes the ceiling field
@@ -1617,6 +1648,8 @@ static void launch_env_step(qa_sim *s, const StepArgs &a, hipStream_t st) {
     static const int helpers_switch = [] { const char *e = getenv("QA_ENV_HELPERS"); return e ? (atoi(e) != 0 ? 1 : 0) : QA_ENV_HELPERS_DEFAULT; }();
     const bool helpers = helpers_switch == 1 || (helpers_switch < 0 && blocks <= s->num_cus);
     const bool xr = s->p.xr_sums != nullptr;           // qa_set_extra_rewards: the XR instantiations
+    // qa_set_self_collision_hips: the SCH instantiations, which live in qa_sim_selfcol.hip
+    if (s->sc_hips) { qa_sch_launch_env_step(hf, s->lean, !hf && helpers, xr, blocks, st, a); return; }
 #define QA_LAUNCH_STEP(PLANE_, LEAN_, HELP_) do { \
         if (xr) hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 1>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); \
         else hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 0>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); } while (0)
@@ -1659,6 +1692,16 @@ int qa_set_terrain_curriculum(qa_sim *s, int64_t *terrain_levels, const int64_t 
     }
     p.terrain_levels = terrain_levels; p.terrain_types = terrain_types; p.terrain_origins = terrain_origins;
     p.terrain_rows = rows; p.terrain_cols = cols; p.terrain_env_length = env_length; p.terrain_episode_s = max_episode_length_s;
+    return QA_OK;
+}
+
+int qa_set_self_collision_hips(qa_sim *s, int on) {
+    if (!s) return QA_E_ARG;
+    if (on && !s->cfg.self_collision) {
+        snprintf(g_err, sizeof(g_err), "qa_set_self_collision_hips: the handle was created with self_collision = 0 (the calf-hip rows belong to the self-collision model)");
+        return QA_E_ARG;
+    }
+    s->sc_hips = on ? 1 : 0;
     return QA_OK;
 }
 
@@ -1705,7 +1748,8 @@ int qa_env_physics_step(qa_sim *s, const float *actions, int32_t delay_steps, vo
     if (!s || !actions || delay_steps < 0 || delay_steps >= QA_ACTION_BUF_LEN) return QA_E_ARG;
     StepArgs a; a.c = s->cfg; a.p = s->p; a.mi = mocap_idx(s); a.actions = actions; a.delay = delay_steps; a.step = 0; a.step_ptr = nullptr; a.prof = nullptr;
     const int blocks = (s->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
-    if (s->cfg.terrain_type == 1) hipLaunchKernelGGL((qa_env_step_kernel<false, 4, 1>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
+    if (s->sc_hips) qa_sch_launch_physics_step(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, a);       // the SCH instantiations (qa_sim_selfcol.hip)
+    else if (s->cfg.terrain_type == 1) hipLaunchKernelGGL((qa_env_step_kernel<false, 4, 1>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 1>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return QA_OK;
@@ -1723,7 +1767,8 @@ static int launch_simulate(qa_sim *s, const float *torques, const uint8_t *cond,
     if (!s) return QA_E_ARG;
     if (!torques) torques = s->p.torques;          // the actuation forces set last (gym keeps applying them)
     const int epb = QA_BLOCK / s->lanes, blocks = (s->cfg.num_envs + epb - 1) / epb;
-    if (s->cfg.terrain_type == 1) hipLaunchKernelGGL((qa_simulate_kernel<false, 4>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, s->cfg, s->p, torques, cond);
+    if (s->sc_hips) qa_sch_launch_simulate(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, s->cfg, s->p, torques, cond);       // the SCH instantiations (qa_sim_selfcol.hip)
+    else if (s->cfg.terrain_type == 1) hipLaunchKernelGGL((qa_simulate_kernel<false, 4>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, s->cfg, s->p, torques, cond);
     else hipLaunchKernelGGL((qa_simulate_kernel<true, 4>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, s->cfg, s->p, torques, cond);
     HIP_TRY(hipGetLastError());
     return QA_OK;
@@ -1835,3 +1880,4 @@ int qa_gae(const float *rewards, const float *values, const uint8_t *dones, cons
 }
 
 }  // extern "C"
+#endif   // QA_SIM_SCH_TU

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from quadrupedal_agility_amd import _capi
-from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import class_to_dict, make_extra_rewards, make_qa_config
+from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import class_to_dict, install_self_collision_hips, make_extra_rewards, make_qa_config
 
 KEY_BODY_NAMES = ["FL_foot", "FR_foot", "RL_foot", "RR_foot"]
 
@@ -74,6 +74,7 @@ class LeggedRobot:
             backend = backend(self.qcfg)          # a factory: the final qa_config (mocap table size, terrain) is only known here
         self.sim = backend
         self.device = str(backend.device)
+        self.self_collision_hips = install_self_collision_hips(cfg, self.sim)      # before anything records a rollout: it selects the kernels
         if self._mocap_table is not None:
             self.sim.set_mocap(*self._mocap_table)
         self._init_buffers()

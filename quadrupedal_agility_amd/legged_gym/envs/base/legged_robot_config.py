@@ -82,6 +82,7 @@ class LeggedRobotCfg(BaseConfig):
         fix_base_link = False
         default_dof_drive_mode = 3
         self_collisions = 0
+        qa_self_collision_hips = False     # include/qa_sim_selfcol.h: also collide each front calf with the rear hip of its side (needs self_collisions == 0)
         replace_cylinder_with_capsule = True
         flip_visual_attachments = True
         density = 0.001

@@ -134,6 +134,20 @@ _NOT_ON_HOT_PATH = {
 }
 
 
+def install_self_collision_hips(cfg, sim):
+    """asset.qa_self_collision_hips -> qa_set_self_collision_hips (include/qa_sim_selfcol.h) on the engine `sim`, for the env classes of both
+    trees.  Call it after the engine is created and before anything records a rollout: a recording bakes the kernel choice in.  Returns
+    whether the feature is on."""
+    if not getattr(cfg.asset, "qa_self_collision_hips", False):
+        return False
+    if getattr(cfg.asset, "self_collisions", 0) != 0:
+        raise ValueError("asset.qa_self_collision_hips needs self-collision enabled (asset.self_collisions == 0): the calf-hip rows belong to that model")
+    if not hasattr(sim, "set_self_collision_hips"):
+        raise NotImplementedError("asset.qa_self_collision_hips needs the HIP engine (qa_set_self_collision_hips); this backend has no twin of it")
+    sim.set_self_collision_hips(True)
+    return True
+
+
 class ExtraRewards:
     """What qa_set_extra_rewards (include/qa_sim_rewards.h) needs besides device buffers: `scale_dt` in _capi.EXTRA_REWARD_NAMES order,
     the two targets, dt as the fp32 step the air time advances by, and the (n, 2) scan grid (None: measured heights are 0)."""

@@ -105,6 +105,13 @@ class QaSim:
         self.api.call("set_extra_rewards", self.h, C.byref(x))
         self.extra_rewards = extra
 
+    def set_self_collision_hips(self, on):
+        """qa_set_self_collision_hips (include/qa_sim_selfcol.h): every kernel that runs physics also collides each front calf with the rear hip
+        of its side; the force lands on CONTACT_FORCES' calf and HIP rows (a hip force > 1 N ends the episode).  Needs cfg.self_collision;
+        it selects other kernels at launch time, so call it before a rollout is recorded."""
+        self.api.call("set_self_collision_hips", self.h, int(bool(on)))
+        self.self_collision_hips = bool(on)
+
     def step_dev(self, actions, delay, step_counter):
         """qa_env_step_dev: the step counter lives in device memory (graph-replayable)."""
         assert actions.is_cuda and actions.dtype == torch.float32 and actions.is_contiguous()

@@ -146,6 +146,7 @@ class LeggedRobotCfg(BaseConfig):
         collapse_fixed_joints = True
         fix_base_link = False
         self_collisions = 0
+        qa_self_collision_hips = False     # include/qa_sim_selfcol.h: also collide each front calf with the rear hip of its side (needs self_collisions == 0)
 
     class domain_rand:
         randomize_friction, friction_range = True, [0.6, 2.0]

@@ -59,6 +59,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
         # store_true flags with default False: the reference's `is not None` test always fires, i.e. the command line DECIDES these two
         env_cfg.obstacle.randomize_start = bool(args.randomize_start)
         env_cfg.obstacle.curriculum = bool(args.curriculum)
+        if getattr(args, "self_collision_hips", False):
+            env_cfg.asset.qa_self_collision_hips = True
     if cfg_train is not None:
         if args.seed is not None:
             cfg_train.seed = args.seed
@@ -104,6 +106,7 @@ def get_args(argv=None):
         p.add_argument("--" + name, type=float)
     for name in ("randomize_start", "curriculum", "randomize_base_mass", "randomize_base_com", "push_robots"):
         p.add_argument("--" + name, action="store_true", default=False)
+    p.add_argument("--self_collision_hips", action="store_true", default=False, help="asset.qa_self_collision_hips = True: a front calf collides with the rear hip of its side (a hip contact ends the episode, as in the reference)")
     p.add_argument("--physics_engine", default="qa")
     p.add_argument("--bbc_path", type=str, default=None, help="behaviour-level model.pt (default: <root>/<runner.bbc_path>)")
     p.add_argument("--log_root", type=str, default="default")
