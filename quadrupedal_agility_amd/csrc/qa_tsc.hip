@@ -8,6 +8,7 @@
 #include <stdio.h>
 
 #include "../../include/qa_sim.h"
+#include "qa_tsc_rewards.h"
 
 extern thread_local char qa_err_buf[512];
 #define g_terr qa_err_buf
@@ -97,12 +98,59 @@ __device__ inline float floor_mod(float a, float b) {
 // term_mask / pen_mask: bit b set = body b is in the termination / penalised list.  Every body's contact-force norm is taken
 // once in a branch-free loop (independent loads, one exposed round trip) and the lists become bit tests; a loop over each
 // list with `||` short-circuits costs one dependent round trip per listed body (11 + 15 of them for the Go2).
-__global__ void __launch_bounds__(TSC_BLOCK) qa_tsc_goal_step_kernel(qa_tsc_goal_cfg c, qa_tsc_goal_io io, uint32_t term_mask, uint32_t pen_mask) {
+//
+// XR: the fourteen extra reward terms of include/qa_tsc_rewards.h.  <false> is the kernel as it was (XrArgs<false> is empty); <true> keeps
+// its style: every (N,12) row a term needs is loaded up front as three 16-byte words (DOF_STATE's row as six), behind branches on the
+// launch arguments only (scale_dt), so no load sits behind a divergent branch and a term that is off costs no memory traffic.
+template <bool XR> struct XrArgs {};
+template <> struct XrArgs<true> { qa_tsc_extra_rewards x; int first_on; };      // first_on: the lowest term index with a non-zero scale
+
+struct Row12 { float4 a, b, d; };
+__device__ inline Row12 load_row12(const float *base, int64_t e) {
+    const float4 *r = reinterpret_cast<const float4 *>(base + e * 12);
+    Row12 o; o.a = r[0]; o.b = r[1]; o.d = r[2];
+    return o;
+}
+__device__ inline void unpack_row12(const Row12 &r, float *out) {
+    out[0] = r.a.x; out[1] = r.a.y; out[2] = r.a.z; out[3] = r.a.w; out[4] = r.b.x; out[5] = r.b.y; out[6] = r.b.z; out[7] = r.b.w;
+    out[8] = r.d.x; out[9] = r.d.y; out[10] = r.d.z; out[11] = r.d.w;
+}
+
+template <bool XR>
+__global__ void __launch_bounds__(TSC_BLOCK) qa_tsc_goal_step_kernel(qa_tsc_goal_cfg c, qa_tsc_goal_io io, uint32_t term_mask, uint32_t pen_mask, XrArgs<XR> xa) {
     const int64_t e = (int64_t)blockIdx.x * TSC_BLOCK + threadIdx.x;
     if (e >= c.num_envs) return;
     const int64_t N = c.num_envs;
     const float *rs = io.root_states + e * 13;
     const float *cf = io.contact_forces + e * c.num_bodies * 3;
+    // the extra terms' inputs: all loads issued here, each (N,12) group behind a uniform branch
+    float x_q[12], x_qd[12], x_prev[12], x_act[12], x_lact[12], x_torg[12], x_ltorg[12], x_sum[QA_TSC_NUM_EXTRA_REWARDS];
+    uint32_t feet_mask = 0;
+    int stumble = 0;
+    if constexpr (XR) {
+        const qa_tsc_extra_rewards &x = xa.x;
+        const float *s = x.scale_dt;
+        const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const Row12 z12 = {z4, z4, z4};
+        Row12 dq0 = z12, dq1 = z12, prev = z12, act = z12, lact = z12, torg = z12, ltorg = z12;
+        if (s[QA_TSC_XR_DOF_ACC] != 0.0f) prev = load_row12(x.prev_dof_vel, e);
+        if (s[QA_TSC_XR_ACTION_RATE] != 0.0f) { act = load_row12(x.actions, e); lact = load_row12(x.prev_actions, e); }
+        if (s[QA_TSC_XR_DELTA_TORQUES] != 0.0f || s[QA_TSC_XR_TORQUE_LIMITS] != 0.0f || s[QA_TSC_XR_TORQUES] != 0.0f) torg = load_row12(x.torques_org, e);
+        if (s[QA_TSC_XR_DELTA_TORQUES] != 0.0f) ltorg = load_row12(x.prev_torques_org, e);
+        // the running sums: a term that is off reads the row of the first term that is on instead (a select on launch arguments, no
+        // branch; its value is never used), so the fourteen loads are independent and unconditional
+#pragma unroll
+        for (int k = 0; k < QA_TSC_NUM_EXTRA_REWARDS; ++k) x_sum[k] = x.extra_episode_sums[(int64_t)(s[k] != 0.0f ? k : xa.first_on) * N + e];
+        // DOF_STATE's 96-byte row last: the compiler de-interleaves it inside the branch, behind a wait that the loads above then share
+        if (s[QA_TSC_XR_DOF_ACC] != 0.0f || s[QA_TSC_XR_DOF_ERROR] != 0.0f || s[QA_TSC_XR_DOF_POS_LIMITS] != 0.0f || s[QA_TSC_XR_DOF_VEL_LIMITS] != 0.0f ||
+            s[QA_TSC_XR_HIP_POS] != 0.0f) { dq0 = load_row12(x.dof_state, 2 * e); dq1 = load_row12(x.dof_state, 2 * e + 1); }      // the 96-byte row of DOF_STATE
+        float il[24];
+        unpack_row12(dq0, il); unpack_row12(dq1, il + 12);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { x_q[k] = il[2 * k]; x_qd[k] = il[2 * k + 1]; }
+        unpack_row12(prev, x_prev); unpack_row12(act, x_act); unpack_row12(lact, x_lact); unpack_row12(torg, x_torg); unpack_row12(ltorg, x_ltorg);
+        if (s[QA_TSC_XR_FEET_STUMBLE] != 0.0f) feet_mask = (1u << c.feet_bodies[0]) | (1u << c.feet_bodies[1]) | (1u << c.feet_bodies[2]) | (1u << c.feet_bodies[3]);
+    }
     const int64_t ep_len = io.episode_length[e] + 1;
     io.episode_length[e] = ep_len;
 
@@ -128,6 +176,8 @@ __global__ void __launch_bounds__(TSC_BLOCK) qa_tsc_goal_step_kernel(qa_tsc_goal
     for (int b = 0; b < c.num_bodies; ++b) {
         const float f = norm3(cf + b * 3);
         over01 |= (uint32_t)(f > 0.1f) << b; over1 |= (uint32_t)(f > 1.0f) << b; over2 |= (uint32_t)(f > 2.0f) << b;
+        // feet_stumble on the row the norm has just read; feet_mask is zero while the term is off (b is uniform: so is the branch)
+        if constexpr (XR) { if ((feet_mask >> b) & 1u) stumble |= qa_rw_feet_stumble_leg(cf[b * 3], cf[b * 3 + 1], cf[b * 3 + 2]); }
     }
     // filtered foot contacts
     bool filt[4];
@@ -218,6 +268,50 @@ __global__ void __launch_bounds__(TSC_BLOCK) qa_tsc_goal_step_kernel(qa_tsc_goal
     const float dyaw = floor_mod((target_yaw - yaw) + PI_F, 2.0f * PI_F) - PI_F;
     term[QA_TSC_REW_TRACKING_YAW] = expf(-fabsf(dyaw));
     term[QA_TSC_REW_TERMINATION] = (reset && !time_out) ? 1.0f : 0.0f;
+    if constexpr (XR) {
+        const qa_tsc_extra_rewards &x = xa.x;
+        float xt[QA_TSC_NUM_EXTRA_REWARDS], bsum[QA_TSC_NUM_REWARDS];
+#pragma unroll
+        for (int k = 0; k < QA_TSC_NUM_REWARDS; ++k) bsum[k] = io.episode_sums[k * N + e];
+        xt[QA_TSC_XR_ACTION_RATE] = qa_tsc_rw_action_rate(x_lact, x_act);
+        xt[QA_TSC_XR_ANG_VEL_XY] = qa_rw_ang_vel_xy(ang[0], ang[1]);
+        xt[QA_TSC_XR_DELTA_TORQUES] = qa_tsc_rw_delta_torques(x_torg, x_ltorg);
+        xt[QA_TSC_XR_DOF_ACC] = qa_tsc_rw_dof_acc(x_prev, x_qd, x.inv_dt);
+        xt[QA_TSC_XR_DOF_ERROR] = qa_tsc_rw_dof_error(x_q, x.default_dof_pos);
+        xt[QA_TSC_XR_DOF_POS_LIMITS] = qa_tsc_rw_dof_pos_limits(x_q, x.dof_pos_lower, x.dof_pos_upper);
+        xt[QA_TSC_XR_DOF_VEL_LIMITS] = qa_tsc_rw_dof_vel_limits(x_qd, x.dof_vel_limit_soft);
+        xt[QA_TSC_XR_EVERY_STEP] = qa_tsc_rw_every_step();
+        xt[QA_TSC_XR_FEET_STUMBLE] = stumble ? 1.0f : 0.0f;
+        xt[QA_TSC_XR_HIP_POS] = qa_tsc_rw_hip_pos(x_q, x.default_dof_pos);
+        xt[QA_TSC_XR_LIN_VEL_Z] = qa_rw_lin_vel_z(lin[2]);
+        xt[QA_TSC_XR_ORIENTATION] = qa_rw_orientation(pg[0], pg[1]);
+        xt[QA_TSC_XR_TORQUE_LIMITS] = qa_tsc_rw_torque_limits(x_torg, x.torque_limit_soft);
+        xt[QA_TSC_XR_TORQUES] = qa_tsc_rw_torques(x_torg);
+        const float total = qa_tsc_rw_total(term, c.reward_scales, bsum, xt, x.scale_dt, x_sum);
+#pragma unroll
+        for (int k = 0; k < QA_TSC_NUM_REWARDS; ++k) io.episode_sums[k * N + e] = bsum[k];
+#pragma unroll
+        for (int k = 0; k < QA_TSC_NUM_EXTRA_REWARDS; ++k) if (x.scale_dt[k] != 0.0f) x.extra_episode_sums[k * N + e] = x_sum[k];
+        io.rew_buf[e] = total;
+        // the reference's :279 / :281, behind reset_idx: every env keeps this step's actions / torques
+        if (x.scale_dt[QA_TSC_XR_ACTION_RATE] != 0.0f) {
+            float4 *o = reinterpret_cast<float4 *>(x.prev_actions + e * 12);
+            o[0] = make_float4(x_act[0], x_act[1], x_act[2], x_act[3]); o[1] = make_float4(x_act[4], x_act[5], x_act[6], x_act[7]);
+            o[2] = make_float4(x_act[8], x_act[9], x_act[10], x_act[11]);
+        }
+        if (x.scale_dt[QA_TSC_XR_DELTA_TORQUES] != 0.0f) {
+            float4 *o = reinterpret_cast<float4 *>(x.prev_torques_org + e * 12);
+            o[0] = make_float4(x_torg[0], x_torg[1], x_torg[2], x_torg[3]); o[1] = make_float4(x_torg[4], x_torg[5], x_torg[6], x_torg[7]);
+            o[2] = make_float4(x_torg[8], x_torg[9], x_torg[10], x_torg[11]);
+        }
+        if (x.scale_dt[QA_TSC_XR_DOF_ACC] != 0.0f) {
+            float4 *o = reinterpret_cast<float4 *>(x.prev_dof_vel + e * 12);
+            float nv[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) nv[k] = qa_tsc_rw_next_prev_dof_vel(x_qd[k], reset);
+            o[0] = make_float4(nv[0], nv[1], nv[2], nv[3]); o[1] = make_float4(nv[4], nv[5], nv[6], nv[7]); o[2] = make_float4(nv[8], nv[9], nv[10], nv[11]);
+        }
+    } else {
     float total = 0.0f;
 #pragma unroll
     for (int k = 0; k < QA_TSC_NUM_REWARDS - 1; ++k) {
@@ -230,6 +324,7 @@ __global__ void __launch_bounds__(TSC_BLOCK) qa_tsc_goal_step_kernel(qa_tsc_goal
     total += rt;
     io.episode_sums[(int64_t)QA_TSC_REW_TERMINATION * N + e] += rt;
     io.rew_buf[e] = total;
+    }
 
     // gather of the goals for the next step
     int64_t g0 = gi < 0 ? 0 : (gi > c.num_goal_slots - 1 ? c.num_goal_slots - 1 : gi);
@@ -507,7 +602,8 @@ int qa_tsc_set_commands(const float *actions, const int64_t *episode_length, int
     return QA_OK;
 }
 
-int qa_tsc_goal_step(const qa_tsc_goal_cfg *cfg, const qa_tsc_goal_io *io, void *stream) {
+// the argument checks of qa_tsc_goal_step, shared with qa_tsc_goal_step_rewards; fills the two body bit sets
+static int goal_step_check(const qa_tsc_goal_cfg *cfg, const qa_tsc_goal_io *io, uint32_t *term_mask_out, uint32_t *pen_mask_out) {
     if (!cfg || !io) { snprintf(g_terr, sizeof(g_terr), "qa_tsc_goal_step: null argument"); return QA_E_ARG; }
     const void *need[] = {io->root_states, io->contact_forces, io->rigid_body_states, io->env_goals, io->obstacle_types, io->x_edge_mask,
                           io->episode_length, io->cur_goal_idx, io->reach_goal_timer, io->last_contacts, io->cur_goals, io->next_goals,
@@ -532,10 +628,53 @@ int qa_tsc_goal_step(const qa_tsc_goal_cfg *cfg, const qa_tsc_goal_io *io, void 
         if (pen_mask & (1u << c.penalised_bodies[k])) { snprintf(g_terr, sizeof(g_terr), "qa_tsc_goal_step: body %d listed twice as penalised", c.penalised_bodies[k]); return QA_E_ARG; }
         pen_mask |= 1u << c.penalised_bodies[k];
     }
-    hipLaunchKernelGGL(qa_tsc_goal_step_kernel, dim3((unsigned)((c.num_envs + TSC_BLOCK - 1) / TSC_BLOCK)), dim3(TSC_BLOCK), 0, (hipStream_t)stream, c, *io,
-                       term_mask, pen_mask);
+    *term_mask_out = term_mask; *pen_mask_out = pen_mask;
+    return QA_OK;
+}
+
+int qa_tsc_goal_step(const qa_tsc_goal_cfg *cfg, const qa_tsc_goal_io *io, void *stream) {
+    uint32_t term_mask = 0, pen_mask = 0;
+    const int rc = goal_step_check(cfg, io, &term_mask, &pen_mask);
+    if (rc != QA_OK) return rc;
+    const qa_tsc_goal_cfg &c = *cfg;
+    hipLaunchKernelGGL(qa_tsc_goal_step_kernel<false>, dim3((unsigned)((c.num_envs + TSC_BLOCK - 1) / TSC_BLOCK)), dim3(TSC_BLOCK), 0, (hipStream_t)stream, c, *io,
+                       term_mask, pen_mask, XrArgs<false>{});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_terr, sizeof(g_terr), "qa_tsc_goal_step: %s", hipGetErrorString(e)); return QA_E_DEVICE; }
+    return QA_OK;
+}
+
+// include/qa_tsc_rewards.h
+int qa_tsc_goal_step_rewards(const qa_tsc_goal_cfg *cfg, const qa_tsc_goal_io *io, const qa_tsc_extra_rewards *extra, void *stream) {
+    bool any = false;
+    if (extra)
+        for (int k = 0; k < QA_TSC_NUM_EXTRA_REWARDS; ++k) any = any || extra->scale_dt[k] != 0.0f;
+    if (!any) return qa_tsc_goal_step(cfg, io, stream);
+    uint32_t term_mask = 0, pen_mask = 0;
+    const int rc = goal_step_check(cfg, io, &term_mask, &pen_mask);
+    if (rc != QA_OK) return rc;
+    const qa_tsc_extra_rewards &x = *extra;
+    const float *s = x.scale_dt;
+    struct Need { const void *ptr; bool on; const char *name; };
+    const bool dof = s[QA_TSC_XR_DOF_ACC] != 0.0f || s[QA_TSC_XR_DOF_ERROR] != 0.0f || s[QA_TSC_XR_DOF_POS_LIMITS] != 0.0f || s[QA_TSC_XR_DOF_VEL_LIMITS] != 0.0f ||
+                     s[QA_TSC_XR_HIP_POS] != 0.0f;
+    const bool torg = s[QA_TSC_XR_DELTA_TORQUES] != 0.0f || s[QA_TSC_XR_TORQUE_LIMITS] != 0.0f || s[QA_TSC_XR_TORQUES] != 0.0f;
+    const Need need[] = {{x.dof_state, dof, "dof_state"}, {x.prev_dof_vel, s[QA_TSC_XR_DOF_ACC] != 0.0f, "prev_dof_vel"},
+                         {x.actions, s[QA_TSC_XR_ACTION_RATE] != 0.0f, "actions"}, {x.prev_actions, s[QA_TSC_XR_ACTION_RATE] != 0.0f, "prev_actions"},
+                         {x.torques_org, torg, "torques_org"}, {x.prev_torques_org, s[QA_TSC_XR_DELTA_TORQUES] != 0.0f, "prev_torques_org"}};
+    for (const Need &n : need) {
+        if (!n.on) continue;
+        if (!n.ptr) { snprintf(g_terr, sizeof(g_terr), "qa_tsc_goal_step_rewards: a term that is on needs %s, which is null", n.name); return QA_E_ARG; }
+        if (((uintptr_t)n.ptr & 15u) != 0) { snprintf(g_terr, sizeof(g_terr), "qa_tsc_goal_step_rewards: %s is not 16-byte aligned", n.name); return QA_E_ARG; }
+    }
+    if (!x.extra_episode_sums) { snprintf(g_terr, sizeof(g_terr), "qa_tsc_goal_step_rewards: extra_episode_sums is null while a term is on"); return QA_E_ARG; }
+    const qa_tsc_goal_cfg &c = *cfg;
+    XrArgs<true> xa; xa.x = x; xa.first_on = 0;
+    while (s[xa.first_on] == 0.0f) ++xa.first_on;                    // `any` holds: it ends
+    hipLaunchKernelGGL(qa_tsc_goal_step_kernel<true>, dim3((unsigned)((c.num_envs + TSC_BLOCK - 1) / TSC_BLOCK)), dim3(TSC_BLOCK), 0, (hipStream_t)stream, c, *io,
+                       term_mask, pen_mask, xa);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_terr, sizeof(g_terr), "qa_tsc_goal_step_rewards: %s", hipGetErrorString(e)); return QA_E_DEVICE; }
     return QA_OK;
 }
 

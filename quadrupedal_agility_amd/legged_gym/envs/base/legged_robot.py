@@ -13,7 +13,7 @@ import numpy as np
 
 import torch
 
-from quadrupedal_agility_amd import _capi
+from quadrupedal_agility_amd import _capi, go2_limits
 from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import class_to_dict, install_self_collision_hips, make_extra_rewards, make_qa_config
 
 KEY_BODY_NAMES = ["FL_foot", "FR_foot", "RL_foot", "RR_foot"]
@@ -189,21 +189,17 @@ class LeggedRobot:
         self.p_gains = torch.full((12,), float(self.qcfg.kp), device=dev)
         self.d_gains = torch.full((12,), float(self.qcfg.kd), device=dev)
         # URDF limits (legged_robot.py:403-430), soft position limits
-        lo = torch.tensor([-1.0472, -1.5708, -2.7227] * 2 + [-1.0472, -0.5236, -2.7227] * 2, device=dev)
-        hi = torch.tensor([1.0472, 3.4907, -0.83776] * 2 + [1.0472, 4.5379, -0.83776] * 2, device=dev)
-        m, r = (lo + hi) / 2, hi - lo
-        s = self.cfg.rewards.soft_dof_pos_limit
-        self.dof_pos_limits = torch.stack([m - 0.5 * r * s, m + 0.5 * r * s], dim=1)
-        self.dof_vel_limits = torch.tensor([30.1, 30.1, 20.07] * 4, device=dev)
-        self.torque_limits = torch.tensor([20.0, 20.0, 40.0] * 4, device=dev)
+        self.dof_pos_limits = go2_limits.soft_dof_pos_limits(self.cfg.rewards.soft_dof_pos_limit, dev)
+        self.dof_vel_limits = torch.tensor(go2_limits.DOF_VEL_LIMITS, device=dev)
+        self.torque_limits = torch.tensor(go2_limits.TORQUE_LIMITS, device=dev)
         self.feet_indices = torch.tensor([_capi.BODY_NAMES.index(n) for n in KEY_BODY_NAMES], device=dev)
         self.penalised_contact_indices = torch.tensor(
             [i for i, n in enumerate(_capi.BODY_NAMES) if any(k in n for k in self.cfg.asset.penalize_contacts_on)], device=dev)
         self.termination_contact_indices = torch.tensor(
             [i for i, n in enumerate(_capi.BODY_NAMES) if any(k in n for k in self.cfg.asset.terminate_after_contacts_on)], device=dev)
-        self.hip_indices = torch.tensor([0, 3, 6, 9], device=dev)
-        self.thigh_indices = torch.tensor([1, 4, 7, 10], device=dev)
-        self.calf_indices = torch.tensor([2, 5, 8, 11], device=dev)
+        self.hip_indices = torch.tensor(go2_limits.HIP_INDICES, device=dev)
+        self.thigh_indices = torch.tensor(go2_limits.THIGH_INDICES, device=dev)
+        self.calf_indices = torch.tensor(go2_limits.CALF_INDICES, device=dev)
         self.prior_prob = torch.ones(self.dim_c, device=dev) / self.dim_c
         self.add_noise = self.cfg.noise.add_noise
         self.noise_scale_vec = self._get_noise_scale_vec(self.cfg)

@@ -6,6 +6,7 @@
   * `qa_env_physics_step` (include/qa_sim.h): action history / delay / clip, 4 x (PD -> articulated-body substep with contact
     against the course's height field), refresh of root / dof / contact-force / rigid-body-state tensors   (:113-139, 231-234)
   * `qa_tsc_goal_step`: episode clock, goal dwell + advance, 7 termination causes, 8 rewards                    (:204-262, 322-346, 412-430)
+    (`qa_tsc_goal_step_rewards`, include/qa_tsc_rewards.h, when rewards.scales sets any of the reference's other 14 terms: all 22)
   * `qa_tsc_reset` + `qa_simulate_if`: reset of the flagged envs and the reference's extra simulate on resets  (:348-410)
   * `qa_tsc_observations`: 132-point scan, the 800 / 671 / 49 rows, history push                                (:432-515, 1708-1755)
 
@@ -16,7 +17,7 @@ hold is stated there (tunnel roof and upper tyre ring: no contact from above; se
 import numpy as np
 import torch
 
-from quadrupedal_agility_amd import _capi
+from quadrupedal_agility_amd import _capi, go2_limits
 from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import class_to_dict, install_self_collision_hips
 from quadrupedal_agility_amd.tsc.legged_gym.obstacle_curriculum import ObstacleCurriculum
 from quadrupedal_agility_amd.tsc.legged_gym.task_level import TaskLevelBookkeeping
@@ -143,6 +144,11 @@ class LeggedRobot:
         self.penalised_contact_indices = torch.tensor([i for i, n in enumerate(names) if any(k in n for k in cfg.asset.penalize_contacts_on)], device=dev)
         self.termination_contact_indices = torch.tensor([i for i, n in enumerate(names) if any(k in n for k in cfg.asset.terminate_after_contacts_on)], device=dev)
         self.key_body_ids = torch.tensor([names.index(n) for n in KEY_BODY_NAMES], device=dev)
+        # _process_dof_props (:596-617): the URDF limits, the position limits made soft
+        self.dof_pos_limits = go2_limits.soft_dof_pos_limits(cfg.rewards.soft_dof_pos_limit, dev)
+        self.dof_vel_limits = torch.tensor(go2_limits.DOF_VEL_LIMITS, device=dev)
+        self.torque_limits = torch.tensor(go2_limits.TORQUE_LIMITS, device=dev)
+        self.hip_indices = torch.tensor(go2_limits.HIP_INDICES, device=dev)
         self.category_mapping = {c: i for i, c in enumerate(cfg.env.mocap_category_all)}
         self.mocap_indices = torch.tensor([self.category_mapping[c] for c in cfg.env.mocap_category], device=dev)
 
@@ -156,8 +162,11 @@ class LeggedRobot:
         self.num_height_points = gx.numel()
         self.height_points = torch.stack([gx.flatten(), gy.flatten(), torch.zeros_like(gx.flatten())], dim=1).contiguous()
         self.bk.init_observations(self.height_samples, self.height_points, self.default_dof_pos, self.default_dof_pos_all, self.key_body_ids.tolist())
+        # (the extra reward terms, if any, are installed by the bookkeeping's constructor: before anything records a rollout)
         self.reward_scales = dict(self.bk.reward_scales)
+        self.reward_names = [n for n in self.bk.reward_names if n != "termination"]
         self.episode_sums = self.bk.episode_sums
+        self._episode_keys = [(n, i) for i, n in enumerate(_capi.TSC_REWARD_NAMES)] + sorted(self.bk.extra_reward_rows.items())
         if cfg.depth.use_camera:
             # attach_camera (:1203-1226): one camera per env on the trunk, pitched down by U(depth.angle) degrees; the draw is keyed
             # by the GLOBAL env id like every other per-env constant, so a sharded job has the cameras of the one-process job
@@ -182,7 +191,7 @@ class LeggedRobot:
         self.cur_obst_idx = torch.zeros(self.num_envs, dtype=torch.long, device=dev)
         self._start_xy = torch.zeros(self.num_envs, 2, device=dev)
         self._start_yaw = torch.zeros(self.num_envs, device=dev)
-        self._episode_means = torch.zeros(len(_capi.TSC_REWARD_NAMES), device=dev)
+        self._episode_means = torch.zeros(self.bk.episode_sums_buf.shape[0], device=dev)
         self._obs_disc_term = torch.zeros(self.num_envs, self.num_obs_disc, device=dev)
         self._all = torch.ones(self.num_envs, dtype=torch.uint8, device=dev)
         self.sync_reset_ids = True
@@ -330,7 +339,8 @@ class LeggedRobot:
             self._step_dev.add_(1)
             if cfg.domain_rand.push_robots:
                 self._push_robots()        # before the goal step: its rewards read the pushed world velocity, as the reference's do (:643-644)
-        bk.post_physics_step(self.root_states, self.contact_forces, self.rigid_body_states, action_hl_history_buf, want_ids=False)
+        bk.post_physics_step(self.root_states, self.contact_forces, self.rigid_body_states, action_hl_history_buf, want_ids=False,
+                             dof_state=self.dof_state, actions=self.actions, torques_org=self.torques_org)
         self.extras["reach_goal"] = bk.reach_goal_cutoff.view(torch.bool)
         flags = bk.reset_buf
         prev_disc = bk.obs_disc_buf.clone()                                  # get_observations_disc() of the envs about to reset (:263)
@@ -353,6 +363,8 @@ class LeggedRobot:
         bk, cfg = self.bk, self.cfg
         ob = cfg.obstacle
         n_goal = cfg.obstacle.num_goals
+        if flags is self._all:
+            bk.zero_prev_buffers()             # a full reset: the reference's last_actions / last_dof_vel / last_torques_org start at zero (:387-389)
         glue = self._glue_kernels() and flags.is_cuda
         if glue:
             if getattr(self, "_start_goal", None) is None:
@@ -393,7 +405,7 @@ class LeggedRobot:
             self._episode_means.copy_(torch.where(cnt > 0, mean, self._episode_means))
             any_reset = (cnt > 0).to(torch.uint8).reshape(1)
         snap = self._episode_means.clone()
-        self.extras["episode"] = {"rew_" + n: snap[i] for i, n in enumerate(_capi.TSC_REWARD_NAMES)}
+        self.extras["episode"] = {"rew_" + n: snap[i] for n, i in self._episode_keys}
         if cfg.env.send_timeouts:
             self.extras["time_outs"] = bk.time_out_buf.view(torch.bool)
         if self.obstacle_curriculum_armed and not first:

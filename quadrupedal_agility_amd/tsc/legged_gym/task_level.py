@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ... import _capi
+from ... import _capi, go2_limits
 
 
 def coarse_depth_maps(height_samples, ceiling_samples, log2_block):
@@ -24,6 +24,41 @@ def coarse_depth_maps(height_samples, ceiling_samples, log2_block):
         x = F.pad(sign * m.to(torch.float32)[None, None], (0, cc * b + 1 - cols, 0, cr * b + 1 - rows), value=sign * fill)
         return (sign * F.max_pool2d(x, kernel_size=b + 1, stride=b))[0, 0].to(torch.int16).contiguous()
     return pooled(height_samples, 1.0, -32768.0), (pooled(ceiling_samples, -1.0, 32767.0) if ceiling_samples is not None else None)
+
+
+def _scale_items(scales):
+    """(name, value) of a rewards.scales class or namespace"""
+    return [(k, getattr(scales, k)) for k in dir(scales) if not k.startswith("_")]
+
+
+def make_tsc_extra_rewards(cfg, dt=None):
+    """qa_tsc_extra_rewards (include/qa_tsc_rewards.h) from the reference's config fields, or None when none of the fourteen extra scales
+    is set (a missing attribute reads as 0): scale * dt as _prepare_reward_function forms it (:1107-1113), the soft limits of :613-616 and
+    the fp32 products limits * soft_*_limit the reference's tensor-times-scalar forms.  A non-zero scale that names none of the 22 terms
+    raises.  The pointers are left NULL: the caller owns the buffers."""
+    scales = cfg.rewards.scales
+    known = set(_capi.TSC_REWARD_NAMES) | set(_capi.TSC_EXTRA_REWARD_NAMES)
+    for name, value in _scale_items(scales):
+        if name not in known and value != 0:
+            raise NotImplementedError(f"reward term {name!r} (rewards.scales.{name} = {value}) is not one of the task-level env's 22 terms: "
+                                      "there is no kernel for it, and it would be ignored")
+    dt = cfg.control.decimation * cfg.sim.dt if dt is None else dt
+    values = [float(getattr(scales, name, 0.0)) for name in _capi.TSC_EXTRA_REWARD_NAMES]
+    if not any(values):
+        return None
+    x = _capi.QaTscExtraRewards()
+    for i, v in enumerate(values):
+        x.scale_dt[i] = v * dt
+    x.inv_dt = float(np.float32(1.0) / np.float32(dt))
+    r = cfg.rewards
+    pos = go2_limits.soft_dof_pos_limits(r.soft_dof_pos_limit)
+    vel = torch.tensor(go2_limits.DOF_VEL_LIMITS) * r.soft_dof_vel_limit
+    tau = torch.tensor(go2_limits.TORQUE_LIMITS) * r.soft_torque_limit
+    for i, name in enumerate(_capi.DOF_NAMES):
+        x.default_dof_pos[i] = float(cfg.init_state.default_joint_angles[name])
+        x.dof_pos_lower[i], x.dof_pos_upper[i] = float(pos[i, 0]), float(pos[i, 1])
+        x.dof_vel_limit_soft[i], x.torque_limit_soft[i] = float(vel[i]), float(tau[i])
+    return x
 
 
 class TaskLevelBookkeeping:
@@ -66,8 +101,22 @@ class TaskLevelBookkeeping:
         self.next_commands = z(n, 6 + self.dim_c)
         self.episode_length_buf, self.cur_goal_idx = z(n, dt=torch.long), z(n, dt=torch.long)
         self.reach_goal_timer, self.last_contacts = z(n), z(n, 4, dt=torch.uint8)
-        self.episode_sums_buf = z(len(_capi.TSC_REWARD_NAMES), n)
-        self.episode_sums = {name: self.episode_sums_buf[i] for i, name in enumerate(_capi.TSC_REWARD_NAMES)}
+        # the fourteen extra terms (include/qa_tsc_rewards.h): ONE buffer of 8 + 14 rows when any is on, so that the reset launches, which
+        # take the row count, cover both sets
+        nb = len(_capi.TSC_REWARD_NAMES)
+        self._extra = make_tsc_extra_rewards(cfg, self.dt)
+        if self._extra is not None and not hasattr(self.lib, self.api.prefix + "tsc_goal_step_rewards"):
+            raise NotImplementedError("rewards.scales sets a term of include/qa_tsc_rewards.h, and this backend has no "
+                                      f"{self.api.prefix}tsc_goal_step_rewards: the scale would be ignored")
+        self.episode_sums_buf = z(nb + (len(_capi.TSC_EXTRA_REWARD_NAMES) if self._extra is not None else 0), n)
+        self.extra_reward_rows = {name: nb + i for i, name in enumerate(_capi.TSC_EXTRA_REWARD_NAMES)
+                                  if self._extra is not None and self._extra.scale_dt[i] != 0.0}
+        # the reference's last_actions / last_torques_org / last_dof_vel as post_physics_step leaves them; the goal step maintains them
+        self.prev_buffers = (z(n, 12), z(n, 12), z(n, 12)) if self._extra is not None else None
+        self.prev_actions, self.prev_torques_org, self.prev_dof_vel = self.prev_buffers or (None, None, None)
+        rows = dict({name: i for i, name in enumerate(_capi.TSC_REWARD_NAMES)}, **self.extra_reward_rows)
+        self.reward_names = sorted(k for k in rows if k != "termination") + ["termination"]
+        self.episode_sums = {name: self.episode_sums_buf[rows[name]] for name in self.reward_names}
         self.base_lin_vel, self.base_ang_vel, self.projected_gravity, self.rpy = z(n, 3), z(n, 3), z(n, 3), z(n, 3)
         self.contact_filt = z(n, 4, dt=torch.uint8)
         self.target_pos_rel, self.next_target_pos_rel, self.target_yaw, self.next_target_yaw = z(n, 2), z(n, 2), z(n), z(n)
@@ -95,10 +144,17 @@ class TaskLevelBookkeeping:
         c.next_goal_threshold, c.leave_goal_threshold = cfg.env.next_goal_threshold, cfg.env.leave_goal_threshold
         c.max_episode_length, c.target_lin_vel = self.max_episode_length, cfg.rewards.target_lin_vel
         c.border_size, c.horizontal_scale = cfg.obstacle.border_size, cfg.obstacle.horizontal_scale
-        self.reward_scales = {}
+        scale_dt = {}
         for i, name in enumerate(_capi.TSC_REWARD_NAMES):                 # _prepare_reward_function :1107-1113: scale * dt
-            self.reward_scales[name] = float(getattr(cfg.rewards.scales, name)) * self.dt
-            c.reward_scales[i] = self.reward_scales[name]
+            scale_dt[name] = float(getattr(cfg.rewards.scales, name)) * self.dt
+            c.reward_scales[i] = scale_dt[name]
+        for name, row in self.extra_reward_rows.items():
+            scale_dt[name] = float(self._extra.scale_dt[row - nb])
+        self.reward_scales = {name: scale_dt[name] for name in self.reward_names}
+
+    def zero_prev_buffers(self):
+        for t in self.prev_buffers or ():
+            t.zero_()
 
     def _gather_cur_goals(self, future=0):
         """legged_robot.py:646-648"""
@@ -118,9 +174,12 @@ class TaskLevelBookkeeping:
             self.latent_eps.data_ptr(), self.latent_c.data_ptr(), self.next_commands.data_ptr(), on=self.device)
         return self.next_commands
 
-    def post_physics_step(self, root_states, contact_forces, rigid_body_states, action_hl_history_buf=None, want_ids=True):
+    def post_physics_step(self, root_states, contact_forces, rigid_body_states, action_hl_history_buf=None, want_ids=True, *, dof_state=None,
+                          actions=None, torques_org=None):
         """The goal / termination / reward part of legged_robot.py:226-273 on the simulator's tensors; returns the ids to reset.
-        The caller's reset then calls `reset_idx(env_ids)`."""
+        The caller's reset then calls `reset_idx(env_ids)`.  With an extra reward term on, the keyword tensors are the simulator's
+        `dof_state` (N*12, 2), `actions`, `torques_org` (N, 12): whichever the terms that are on read.  The previous step's actions, torques
+        and joint velocities are this object's own buffers (`prev_actions`, `prev_torques_org`, `prev_dof_vel`), which the launch maintains."""
         keep = [t.to(self.device, torch.float32).contiguous() for t in (root_states, contact_forces, rigid_body_states)]
         io = _capi.QaTscGoalIo()
         io.root_states, io.contact_forces, io.rigid_body_states = (t.data_ptr() for t in keep)
@@ -139,7 +198,19 @@ class TaskLevelBookkeeping:
                        rew_buf=self.rew_buf)
         for name, t in members.items():
             setattr(io, name, t.data_ptr())
-        self.api.launch("tsc_goal_step", C.byref(self._cfg), C.byref(io), on=self.device)
+        if self._extra is None:
+            self.api.launch("tsc_goal_step", C.byref(self._cfg), C.byref(io), on=self.device)
+        else:
+            x, nb = self._extra, len(_capi.TSC_REWARD_NAMES)
+            given = dict(dof_state=dof_state, actions=actions, torques_org=torques_org)
+            for name, t in given.items():
+                if t is not None:
+                    t = t.to(self.device, torch.float32).contiguous()
+                    keep.append(t)
+                setattr(x, name, t.data_ptr() if t is not None else None)          # a term that is on and lacks its tensor: the entry point says which
+            x.prev_actions, x.prev_torques_org, x.prev_dof_vel = (t.data_ptr() for t in self.prev_buffers)
+            x.extra_episode_sums = self.episode_sums_buf[nb:].data_ptr()
+            self.api.launch("tsc_goal_step_rewards", C.byref(self._cfg), C.byref(io), C.byref(x), on=self.device)
         self.roll, self.pitch, self.yaw = self.rpy[:, 0], self.rpy[:, 1], self.rpy[:, 2]
         return self.reset_buf.nonzero(as_tuple=False).flatten() if want_ids else None          # nonzero() is a host sync
 
@@ -256,6 +327,8 @@ class TaskLevelBookkeeping:
             self.reach_goal_timer[env_ids] = 0
             self.episode_sums_buf[:, env_ids] = 0
             self.episode_length_buf[env_ids] = 0
+            if self.prev_buffers is not None and len(env_ids) == self.num_envs:      # a full reset: the three start at zero (:387-389)
+                self.zero_prev_buffers()
             self.cur_goals[env_ids] = self.env_goals[env_ids, 0]
             self.next_goals[env_ids] = self.env_goals[env_ids, 1]
 

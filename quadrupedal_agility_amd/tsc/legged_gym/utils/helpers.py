@@ -61,6 +61,17 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
         env_cfg.obstacle.curriculum = bool(args.curriculum)
         if getattr(args, "self_collision_hips", False):
             env_cfg.asset.qa_self_collision_hips = True
+        for item in getattr(args, "reward_scale", None) or []:
+            name, eq, value = item.partition("=")
+            if not hasattr(env_cfg.rewards.scales, name):
+                raise ValueError(f"--reward_scale {item}: rewards.scales has no term {name!r}")
+            try:
+                scale = float(value) if eq else None
+            except ValueError:
+                scale = None
+            if scale is None:
+                raise ValueError(f"--reward_scale {item}: expected NAME=VALUE with a number for VALUE")
+            setattr(env_cfg.rewards.scales, name, scale)
     if cfg_train is not None:
         if args.seed is not None:
             cfg_train.seed = args.seed
@@ -107,6 +118,8 @@ def get_args(argv=None):
     for name in ("randomize_start", "curriculum", "randomize_base_mass", "randomize_base_com", "push_robots"):
         p.add_argument("--" + name, action="store_true", default=False)
     p.add_argument("--self_collision_hips", action="store_true", default=False, help="asset.qa_self_collision_hips = True: a front calf collides with the rear hip of its side (a hip contact ends the episode, as in the reference)")
+    p.add_argument("--reward_scale", action="append", default=[], metavar="NAME=VALUE",
+                   help="rewards.scales.NAME = VALUE for any of the reference's 22 terms (repeatable), e.g. --reward_scale torques=-1e-5")
     p.add_argument("--physics_engine", default="qa")
     p.add_argument("--bbc_path", type=str, default=None, help="behaviour-level model.pt (default: <root>/<runner.bbc_path>)")
     p.add_argument("--log_root", type=str, default="default")
