@@ -1,4 +1,5 @@
-/* qa_sim_selfcol.h -- extension of include/qa_sim.h: each front calf collides with the rear hip of its side inside the physics substep.
+/* qa_sim_selfcol.h -- extension of include/qa_sim.h: each front calf collides with the rear hip of its side inside the physics substep, and
+ * (a second switch) each calf of a front / rear pair with the other leg's thigh.
  *
  * Kept apart from qa_sim.h for the reason qa_sim_rewards.h is: that header is the ABI the CPU oracle twins symbol by symbol
  * (tests/test_abi.py), and this feature adds neither an arena tensor nor a config field to it.  The library exports the entry point next to
@@ -31,6 +32,20 @@ extern "C" {
  * bakes it in.  Call this BEFORE the first recording, and record again after changing it.
  * Returns QA_E_ARG on a NULL handle and, with on != 0, on a handle created with cfg.self_collision == 0. */
 int qa_set_self_collision_hips(qa_sim *sim, int on);
+
+/* The next pair class: a calf against the THIGH of the front / rear neighbour of its side.  The thigh is the URDF's thigh box 0.11 x 0.0245 x 0.034
+ * as its circumscribed capsule (segment (0, 0, -0.0515) .. (0, 0, -0.1615) of the thigh link, radius 21 mm).  The joint limits prune none of the
+ * twelve ordered (calf leg, thigh leg) relations; the four front / rear relations of the same side get a row -- FL calf on RL thigh, RL calf on
+ * FL thigh, FR calf on RR thigh, RR calf on FR thigh -- and the left / right and diagonal relations stay unmodelled.
+ *   - One internal level serves both setters: 0 none, 1 calf-hip rows, 2 calf-hip and calf-thigh rows.  qa_set_self_collision_hips(on) sets it
+ *     to on ? 1 : 0; this call sets it to 2 with on != 0, and from 2 back to 1 with on == 0 (levels 0 and 1 stay as they are).
+ *   - Two more frictionless rows per front / rear pair, with the calf-hip row's activity and bias rules.
+ *   - CONTACT_FORCES carries the force on the calf body (5 + 4 leg) and its opposite on the THIGH body (4 + 4 other leg): the collision
+ *     penalty and the task-level masks read it; no termination follows from it.
+ *   - While no calf-thigh pair is inside the contact offset every arena tensor is bit-identical to level 1.
+ * Like the call above it selects kernel instantiations: call it BEFORE the first recording, and record again after changing it.
+ * Returns QA_E_ARG on a NULL handle and, with on != 0, on a handle created with cfg.self_collision == 0. */
+int qa_set_self_collision_thighs(qa_sim *sim, int on);
 
 #ifdef __cplusplus
 }

@@ -281,6 +281,9 @@ struct ContactOut {
     // direction of its force on THIS leg's body -- the calf of a front leg, the hip of a rear leg.  The kernels turn them into a force behind
     // phys_substep: the block below that reports the other forces stays the same code with and without the rows
     float sh_lam; V3 sh_dir;
+    // SCH = 2 only (calf against the front / rear neighbour's thigh): the same pair of values per row -- row 0 is the front leg's calf on the rear
+    // leg's thigh, row 1 the rear leg's calf on the front leg's thigh; the direction is that of the force on THIS leg's calf or thigh
+    float st_lam[2]; V3 st_dir[2];
 };
 
 // Self-collision (the reference enables it: bbc/.../go2_locomotion_config.py:72, tsc/.../go2_agility_config.py:43 `self_collisions = 0`): the
@@ -400,6 +403,9 @@ __device__ long long *g_subprof = nullptr;
 #define QA_PRIV_FLOATS 180
 #define QA_PRIV_HIPS 180                 // SCH instantiations: 1 calf-hip row x 20 floats behind the records above ...
 #define QA_PRIV_FLOATS_SCH 204           // ... and a lane stride that is again an odd number of 16-byte records (51)
+#define QA_PRIV_THIGHS 200               // SCH = 2: 2 calf-thigh rows x 20 floats behind the calf-hip row ...
+#define QA_PRIV_FLOATS_SCT 244           // ... lane stride 61 records, odd again
+#define QA_PRIV_FLOATS_OF(SCH) ((SCH) >= 2 ? QA_PRIV_FLOATS_SCT : (SCH) ? QA_PRIV_FLOATS_SCH : QA_PRIV_FLOATS)
 struct LRow { float *p; };               // row view in LDS
 QA_DEV float &lr(float *priv, int k) { return priv[k * QA_PRIV_STRIDE]; }
 
@@ -534,7 +540,7 @@ QA_DEV void prow_load(const float *rec, PRow &r) {
     r.m[0] = f2{c.z, c.w}; r.m[1] = f2{d.x, d.y}; r.m[2] = f2{d.z, d.w}; r.m[3] = f2{e.x, e.y}; r.m[4] = f2{e.z, 0.f}; r.dinv = e.w;
 }
 template <int SCH = 0>
-QA_DEV float *priv_of(float *s_priv, int tix) { return s_priv + tix * (SCH ? QA_PRIV_FLOATS_SCH : QA_PRIV_FLOATS); }
+QA_DEV float *priv_of(float *s_priv, int tix) { return s_priv + tix * QA_PRIV_FLOATS_OF(SCH); }
 // the reported force of the calf-hip row (SCH): +n on the front leg's calf (body 5 + 4 leg), -n on the rear leg's hip (body 3 + 4 leg)
 QA_DEV void sch_forces(const ContactOut &co, float dt, int leg, V3 &hip_f, V3 &calf_f) {
     const V3 f = (co.sh_lam * (1.0f / dt)) * co.sh_dir;
@@ -543,6 +549,43 @@ QA_DEV void sch_forces(const ContactOut &co, float dt, int leg, V3 &hip_f, V3 &c
     const V3 h = hip_f + f, c = calf_f + f;
     hip_f = calf ? hip_f : h;
     calf_f = calf ? c : calf_f;
+}
+// the reported forces of the two calf-thigh rows (SCH = 2): +n on the calf (body 5 + 4 leg) of the row's calf leg, -n on the THIGH (body 4 + 4 leg)
+// of the other leg.  A row that carried no impulse leaves both forces untouched, bit for bit.
+QA_DEV void sct_forces(const ContactOut &co, float dt, int leg, V3 &thigh_f, V3 &calf_f) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const V3 f = (co.st_lam[r] * (1.0f / dt)) * co.st_dir[r];
+        const bool live = co.st_lam[r] != 0.f, calf = ((leg & 2) == 0) == (r == 0);
+        const V3 t = thigh_f + f, c = calf_f + f;
+        thigh_f = (live && !calf) ? t : thigh_f;
+        calf_f = (live && calf) ? c : calf_f;
+    }
+}
+// One frictionless row between two bodies of a front / rear pair of legs (lane ^ 2), from this lane's joint Jacobian jl of the row: the algebra of
+// the calf-calf and calf-hip rows (no base Jacobian of its own; base part and effective mass summed over the two lanes), stored as a packed record.
+QA_DEV void pair_row_store(float *rec, const float jl[3], const float *G, const float *Linv, const float *Binv, float gap, float dt, float max_depen) {
+    Row r;
+    float h[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) h[i] = G[0 * 6 + i] * jl[0] + G[1 * 6 + i] * jl[1] + G[2 * 6 + i] * jl[2];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) r.jh[i] = h[i] + dpp_f<0x4E>(h[i]);
+    sym6_mul(Binv, r.jh, r.bj);
+    r.lj[0] = Linv[0] * jl[0] + Linv[1] * jl[1] + Linv[2] * jl[2];
+    r.lj[1] = Linv[1] * jl[0] + Linv[3] * jl[1] + Linv[4] * jl[2];
+    r.lj[2] = Linv[2] * jl[0] + Linv[4] * jl[1] + Linv[5] * jl[2];
+    const float dleg = jl[0] * r.lj[0] + jl[1] * r.lj[1] + jl[2] * r.lj[2];
+    float d = dleg + dpp_f<0x4E>(dleg);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) d = fmaf(r.jh[i], r.bj[i], d);
+    const float g = gap / dt;
+    PRow pr_;
+    pr_.j[0] = f2{r.jh[0], r.jh[1]}; pr_.j[1] = f2{r.jh[2], r.jh[3]}; pr_.j[2] = f2{r.jh[4], r.jh[5]}; pr_.j[3] = f2{jl[0], jl[1]};
+    pr_.j[4] = f2{jl[2], gap >= 0.f ? g : fmaxf(g, -max_depen)};
+    pr_.m[0] = f2{r.bj[0], r.bj[1]}; pr_.m[1] = f2{r.bj[2], r.bj[3]}; pr_.m[2] = f2{r.bj[4], r.bj[5]}; pr_.m[3] = f2{r.lj[0], r.lj[1]}; pr_.m[4] = f2{r.lj[2], 0.f};
+    pr_.dinv = 1.0f / (d + QA_CFM);
+    prow_store(rec, pr_);
 }
 // env-step persistents parked between substeps (act3 sp3 sd3 binert10) as five 16-byte records at QA_PRIV_STEP
 QA_DEV void priv_park(float *priv, const float *act, const float *sp, const float *sd, const float *bi) {
@@ -1023,6 +1066,46 @@ QA_DEV void phys_substep(EnvState &st, const float *tbl, const float *btbl, cons
             prow_store(priv + QA_PRIV_HIPS, pr_);
         }
     }
+    // ---- calf against the front / rear neighbour's thigh (SCH = 2): the same pair, lane ^ 2, with two rows -- row 0 the front leg's calf on the rear
+    // leg's thigh, row 1 the rear leg's calf on the front leg's thigh.  Each lane sends its calf and its thigh segment and both evaluate
+    // qa_sc_calf_thigh on the same role-ordered points (calf first), so they agree bit for bit.  Chain depth 3 on the calf's side, 2 on the thigh's
+    // (the calf joint does not move the thigh).  One vote for both rows: rarer than the calf-hip row's build is cheap.
+    bool st_on[2] = {false, false}, any_st = false;
+    float st_lam[2] = {0.f, 0.f};
+    if constexpr (SCH >= 2) {
+        const float torg[3] = {o[1].x, o[1].y, o[1].z}, knee[3] = {o[2].x, o[2].y, o[2].z};
+        float th0[3], th1[3];
+        qa_sc_thigh_segment(torg, knee, th0, th1);
+        const float own[12] = {o[2].x, o[2].y, o[2].z, foot_p.x, foot_p.y, foot_p.z, th0[0], th0[1], th0[2], th1[0], th1[1], th1[2]};
+        float oth[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) oth[i] = dpp_f<0x4E>(own[i]);
+        qa_sc_contact ct[2];
+        V3 st_nw[2];
+        bool st_calf[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            st_calf[r] = sh_calf == (r == 0);                 // this lane holds the row's calf
+            float cs[6], ts[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) { cs[i] = st_calf[r] ? own[i] : oth[i]; ts[i] = st_calf[r] ? oth[6 + i] : own[6 + i]; }
+            qa_sc_calf_thigh(cs, cs + 3, ts, ts + 3, &ct[r]);
+            st_on[r] = ct[r].gap < P.contact_offset;
+            const float sg = st_calf[r] ? 1.f : -1.f;
+            st_nw[r] = v3(sg * ct[r].n[0], sg * ct[r].n[1], sg * ct[r].n[2]);       // base frame: direction of the force on THIS leg's body
+            co.st_dir[r] = mul(R, st_nw[r]);
+        }
+        any_st = __any(st_on[0] || st_on[1]);
+        if (any_st) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const V3 pm = st_calf[r] ? v3(ct[r].pc[0], ct[r].pc[1], ct[r].pc[2]) : v3(ct[r].ph[0], ct[r].ph[1], ct[r].ph[2]);
+                const float jl[3] = {dot(st_nw[r], cross(ax[0], pm - o[0])), dot(st_nw[r], cross(ax[1], pm - o[1])),
+                                     st_calf[r] ? dot(st_nw[r], cross(ax[2], pm - o[2])) : 0.f};
+                pair_row_store(priv + QA_PRIV_THIGHS + 20 * r, jl, G, Linv, Binv, ct[r].gap, dt, P.max_depen);
+            }
+        }
+    }
     // joint limits: at most one stop per joint can be within the margin.  jl = sgn e_k  =>  jh = sgn G[k,:], lj = sgn Linv[:,k]
     float lim_sgn[3], lim_bias[3], lim_lam[3], lim_dinv[3];   // registers: these rows run in most waves
     f2 lim_m[3][3];
@@ -1192,6 +1275,28 @@ QA_DEV void phys_substep(EnvState &st, const float *tbl, const float *btbl, cons
                 x[0] += f2{quad_sum(db0.x), quad_sum(db0.y)}; x[1] += f2{quad_sum(db1.x), quad_sum(db1.y)}; x[2] += f2{quad_sum(db2.x), quad_sum(db2.y)};
             }
         }
+        // calf-thigh pairs (SCH = 2): a fourth pair phase, its two rows one after the other, each with the vote, the ordering and the dl = 0 of the
+        // calf-hip phase; the front lane of a pair reports the base-velocity change of both rows
+        if constexpr (SCH >= 2) {
+            if (any_st) {
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    PRow r; prow_load(priv + QA_PRIV_THIGHS + 20 * k, r);
+                    const float tl = r.j[3].x * x[3].x + r.j[3].y * x[3].y + r.j[4].x * x[4].x;
+                    const float tls = tl + dpp_f<0x4E>(tl);
+                    float res = r.j[4].y + tls;
+                    res = fmaf(r.j[0].x, x[0].x, res); res = fmaf(r.j[0].y, x[0].y, res); res = fmaf(r.j[1].x, x[1].x, res);
+                    res = fmaf(r.j[1].y, x[1].y, res); res = fmaf(r.j[2].x, x[2].x, res); res = fmaf(r.j[2].y, x[2].y, res);
+                    const float lam = st_on[k] ? fmaxf(st_lam[k] - res * r.dinv, 0.f) : st_lam[k], dl = lam - st_lam[k];
+                    st_lam[k] = lam;
+                    x[3] = pfma(r.m[3], f2s(dl), x[3]);
+                    x[4].x = fmaf(r.m[4].x, dl, x[4].x);
+                    const float dlb = sh_calf ? dl : 0.f;
+                    const f2 db0 = r.m[0] * f2s(dlb), db1 = r.m[1] * f2s(dlb), db2 = r.m[2] * f2s(dlb);
+                    x[0] += f2{quad_sum(db0.x), quad_sum(db0.y)}; x[1] += f2{quad_sum(db1.x), quad_sum(db1.y)}; x[2] += f2{quad_sum(db2.x), quad_sum(db2.y)};
+                }
+            }
+        }
     }
     ub[0] = x[0].x; ub[1] = x[0].y; ub[2] = x[1].x; ub[3] = x[1].y; ub[4] = x[2].x; ub[5] = x[2].y;
     w[0] = x[3].x; w[1] = x[3].y; w[2] = x[4].x;
@@ -1248,6 +1353,7 @@ QA_DEV void phys_substep(EnvState &st, const float *tbl, const float *btbl, cons
         for (int pr = 0; pr < 2; ++pr) if (any_sc[pr] && sc_on[pr]) co.self_f = co.self_f + (sc_lam[pr] * idt) * mul(R, sc_nw[pr]);
     }
     if constexpr (SCH != 0) co.sh_lam = sh_lam;          // only ever changed under sh_on: 0 for a lane whose pair is apart
+    if constexpr (SCH >= 2) { co.st_lam[0] = st_lam[0]; co.st_lam[1] = st_lam[1]; }
     // ---- what the contacts do to the articulated obstacles' joints: generalised force -f_n ca, summed over the quad, kept per env in LDS
     if (!PLANE && T.ob_acc) {
         float ga[QA_OBST_PER_ENV];

@@ -1,6 +1,7 @@
-// qa_selfcol.h -- the geometry of the calf-against-neighbouring-hip self-collision class (include/qa_sim_selfcol.h), ONCE, for
-// host and device: phys_substep (qa_physics.h) calls these functions with base-frame points it holds in registers, and the host twin of
-// tests/c_host/qa_selfcol_host.cpp calls the same functions on plain arrays.  Plain floats in, plain floats out.
+// qa_selfcol.h -- the geometry of the calf-against-neighbouring-hip and calf-against-neighbouring-thigh self-collision classes
+// (include/qa_sim_selfcol.h), ONCE, for host and device: phys_substep (qa_physics.h) calls these functions with base-frame points
+// it holds in registers, and the host twins tests/c_host/qa_selfcol_host.cpp and qa_selfcol_thighs_host.cpp call the same functions on plain
+// arrays.  Plain floats in, plain floats out.
 //
 // Shapes, base frame: the calf is the capsule of the calf-calf class (knee to foot centre, radius QA_CALF_RADIUS at the knee growing to
 // QA_FOOT_RADIUS at the foot); the hip is the URDF's hip cylinder taken as a capsule -- segment (0, +-0.06, 0) .. (0, +-0.10, 0) in the hip
@@ -75,6 +76,42 @@ QA_SC_FN void qa_sc_calf_hip(const float knee[3], const float foot[3], const flo
     const float inv = dist > 1e-6f ? 1.0f / dist : 0.f;
     out->n[0] = dv[0] * inv; out->n[1] = dv[1] * inv; out->n[2] = dist > 1e-6f ? dv[2] * inv : 1.f;      // coincident axes: any unit vector
     out->gap = dist - (QA_CALF_RADIUS + s * (QA_FOOT_RADIUS - QA_CALF_RADIUS)) - QA_HIP_CAP_RADIUS;
+    out->s = s; out->t = t;
+}
+
+// ---- calf against the thigh of the front / rear neighbour (qa_set_self_collision_thighs).  The thigh is the URDF's thigh box
+// 0.11 x 0.0245 x 0.034 taken as its circumscribed capsule: segment (0, 0, -0.0515) .. (0, 0, -0.1615) in the thigh link's frame, radius 21 mm.
+// The knee sits at (0, 0, -0.213) of that frame, so the segment lies on the line thigh joint origin -> knee at these two fractions of it.
+#define QA_THIGH_CAP_RADIUS 0.021f
+#define QA_THIGH_CAP_F0 (0.0515f / 0.213f)
+#define QA_THIGH_CAP_F1 (0.1615f / 0.213f)
+
+// the thigh capsule's segment from the thigh joint origin and the knee (base frame)
+QA_SC_FN void qa_sc_thigh_segment(const float thigh_org[3], const float knee[3], float t0[3], float t1[3]) {
+    QA_SC_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        const float d = knee[i] - thigh_org[i];
+        t0[i] = thigh_org[i] + QA_THIGH_CAP_F0 * d;
+        t1[i] = thigh_org[i] + QA_THIGH_CAP_F1 * d;
+    }
+}
+
+// calf capsule (knee, foot) against thigh capsule (t0, t1): qa_sc_calf_hip's expressions with the thigh's radius.  Operands by ROLE (calf first);
+// in the result t, ph and n refer to the thigh where the hip's comments say hip.
+QA_SC_FN void qa_sc_calf_thigh(const float knee[3], const float foot[3], const float t0[3], const float t1[3], qa_sc_contact *out) {
+    float s, t;
+    qa_sc_segment_closest(knee, foot, t0, t1, &s, &t);
+    float dv[3];
+    QA_SC_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        out->pc[i] = knee[i] + s * (foot[i] - knee[i]);
+        out->ph[i] = t0[i] + t * (t1[i] - t0[i]);
+        dv[i] = out->pc[i] - out->ph[i];
+    }
+    const float dist = sqrtf(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
+    const float inv = dist > 1e-6f ? 1.0f / dist : 0.f;
+    out->n[0] = dv[0] * inv; out->n[1] = dv[1] * inv; out->n[2] = dist > 1e-6f ? dv[2] * inv : 1.f;      // coincident axes: any unit vector
+    out->gap = dist - (QA_CALF_RADIUS + s * (QA_FOOT_RADIUS - QA_CALF_RADIUS)) - QA_THIGH_CAP_RADIUS;
     out->s = s; out->t = t;
 }
 

@@ -33,10 +33,16 @@ static_assert(QA_NUM_LEG_PTS == QA_LEG_PTS && QA_NUM_BASE_PTS == QA_BASE_PTS, "m
 // with QA_SIM_SCH_TU defined it contributes only the kernel templates, which that file instantiates with SCH = 1 (qa_set_self_collision_hips) behind
 // the qa_sch_* launchers declared below: instantiating them HERE, next to the others, changed the code the compiler generated for the existing
 // kernels (same instructions, another schedule and register assignment), and those are to stay exactly as they are.  A code object has its own
-// constant memory, so the second translation unit keeps its own copy of the table (qa_sch_upload_table).
+// constant memory, so the second translation unit keeps its own copy of the table (qa_sch_upload_table).  qa_sim_selfcol_thighs.hip is a third
+// one of the same kind: SCH = 2 (qa_set_self_collision_thighs) behind the qa_sct_* launchers, QA_SCH_LEVEL = 2.
 #ifdef QA_SIM_SCH_TU
+#if defined(QA_SCH_LEVEL) && QA_SCH_LEVEL == 2
+#define c_tbl c_tbl_sct
+#define g_subprof g_subprof_sct
+#else
 #define c_tbl c_tbl_sch
 #define g_subprof g_subprof_sch
+#endif
 #endif
 __constant__ float c_tbl[QA_TBL_FLOATS];
 
@@ -124,7 +130,7 @@ struct qa_sim {
     long long *prof = nullptr;
     int lanes = 4;                 // lanes per env of the step / simulate kernels (one quad: lane & 3 = leg)
     int lean = 0;                  // qa_set_lean_exports
-    int sc_hips = 0;               // qa_set_self_collision_hips: the SCH instantiations of the step / simulate kernels
+    int sc_hips = 0;               // SCH level of the step / simulate kernels: 1 qa_set_self_collision_hips, 2 qa_set_self_collision_thighs on top of it
     int num_cus = 256;             // compute units of the device the arena lives on (launch_env_step: helper wavefronts by launch size)
     qa_config cfg;
     Layout L;
@@ -923,7 +929,8 @@ QA_DEV void shift_history_store(const Ptrs &p, int bix, int lane, int N, float (
 // HELP = 1 (plane kernels): two helper wavefronts per workgroup take the bias forces and the contact candidates of every substep off the env's own
 // wavefront (phys_substep ROLE 1 / 2 / 3, qa_physics.h) -- three of a CU's four SIMDs idle otherwise at one wavefront per CU.
 // SCH = 1 (qa_set_self_collision_hips): the substeps also collide each front calf with the rear hip of its side; one more 16-byte-aligned row record
-// per lane in LDS (46 -> 52 KB of private slots per workgroup).  The SCH = 0 instantiations are the kernels as they were.
+// per lane in LDS (46 -> 52 KB of private slots per workgroup).  SCH = 2 (qa_set_self_collision_thighs): and each calf of a front / rear pair with the
+// other leg's thigh; two more records (61 KB).  The SCH = 0 instantiations are the kernels as they were.
 template <bool PLANE, int LPE, int MODE = 0, int LEAN = 0, int HELP = 0, int XR = 0, int SCH = 0>
 __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(StepArgs a) {
     static_assert(XR == 0 || MODE == 0, "the extra reward terms belong to the behaviour-level post-physics phase");
@@ -942,7 +949,7 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
     // holds -- 160 KB per CU -- and with it the throughput once there are more workgroups than CUs):
     //   physics phase:      per-lane private slots | terrain windows (height field only)
     //   observation phase:  per-env staging | OBS_GROUP assembled observation rows
-    constexpr int PRIV_FLOATS = SCH ? QA_PRIV_FLOATS_SCH : QA_PRIV_FLOATS;
+    constexpr int PRIV_FLOATS = QA_PRIV_FLOATS_OF(SCH);
     constexpr int U_PHYS = PRIV_FLOATS * QA_PRIV_STRIDE + (PLANE ? 0 : EPB * QA_PATCH * QA_PATCH + EPB * QA_OB_LDS);
     constexpr int U_OBS = EPB * S_ENV + OBS_GROUP * S_ROW;
     constexpr int U_ALL = ((U_PHYS > U_OBS ? U_PHYS : U_OBS) + 3) & ~3;
@@ -1202,6 +1209,7 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
     }
     V3 hip_f = on_body(myb), thigh_f = on_body(myb + 1), calf_f = on_body(myb + 2) + co.self_f;
     if constexpr (SCH != 0) sch_forces(co, c.sim_dt, leg, hip_f, calf_f);          // a neighbour's calf on this leg's hip: check_termination sees it below
+    if constexpr (SCH >= 2) sct_forces(co, c.sim_dt, leg, thigh_f, calf_f);        // a neighbour's calf on this leg's thigh and back: the collision penalty sees it
     if (valid && !(LEAN & 1)) {
         float *cf = p.cforce + (int64_t)env * 57, *rb = p.rbpos + (int64_t)env * 57;
         float *m = cf + 3 * myb;
@@ -1390,7 +1398,7 @@ template <bool PLANE, int LPE, int SCH = 0>
 __global__ void __launch_bounds__(QA_BLOCK) qa_simulate_kernel(qa_config c, Ptrs p, const float *torques, const uint8_t *cond) {
     if (cond && *cond == 0) return;               // qa_simulate_if: the whole launch is a no-op (uniform over the grid)
     __shared__ float s_tbl[QA_TBL_FLOATS];
-    __shared__ __attribute__((aligned(16))) float s_priv[(SCH ? QA_PRIV_FLOATS_SCH : QA_PRIV_FLOATS) * QA_PRIV_STRIDE];
+    __shared__ __attribute__((aligned(16))) float s_priv[QA_PRIV_FLOATS_OF(SCH) * QA_PRIV_STRIDE];
     __shared__ float s_patch[PLANE ? 1 : ENVS_PER_BLOCK * QA_PATCH * QA_PATCH];
     __shared__ float s_ob[PLANE ? 1 : ENVS_PER_BLOCK * QA_OB_LDS];
     static_assert(LPE == 4, "one quad per env");
@@ -1444,6 +1452,7 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_simulate_kernel(qa_config c, Ptrs
         V3 f = on_body(myb + k);
         if (k == 2) f = f + co.self_f;
         if constexpr (SCH != 0) { V3 hf_ = z, cf_ = z; sch_forces(co, c.sim_dt, leg, hf_, cf_); if (k == 0) f = f + hf_; if (k == 2) f = f + cf_; }
+        if constexpr (SCH >= 2) { V3 tf_ = f, cf_ = f; sct_forces(co, c.sim_dt, leg, tf_, cf_); f = k == 1 ? tf_ : (k == 2 ? cf_ : f); }
         cf[3 * (myb + k)] = f.x; cf[3 * (myb + k) + 1] = f.y; cf[3 * (myb + k) + 2] = f.z;
         V3 w = mul(R, org[k]) + st.pos; rb[3 * (myb + k)] = w.x; rb[3 * (myb + k) + 1] = w.y; rb[3 * (myb + k) + 2] = w.z;
     }
@@ -1467,6 +1476,11 @@ int qa_sch_upload_table(const float *tbl, size_t bytes);
 void qa_sch_launch_env_step(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a);
 void qa_sch_launch_physics_step(bool hf, int blocks, hipStream_t st, const StepArgs &a);
 void qa_sch_launch_simulate(bool hf, int blocks, hipStream_t st, const qa_config &c, const Ptrs &p, const float *torques, const uint8_t *cond);
+// and of the SCH = 2 instantiations (qa_sim_selfcol_thighs.hip)
+int qa_sct_upload_table(const float *tbl, size_t bytes);
+void qa_sct_launch_env_step(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a);
+void qa_sct_launch_physics_step(bool hf, int blocks, hipStream_t st, const StepArgs &a);
+void qa_sct_launch_simulate(bool hf, int blocks, hipStream_t st, const qa_config &c, const Ptrs &p, const float *torques, const uint8_t *cond);
 
 #ifndef QA_SIM_SCH_TU
 // ------------------------------------------------------------------ fused GAE (rollout_storage.py:97-111)
@@ -1602,7 +1616,7 @@ int qa_create(const qa_config *cfg, void *arena, int64_t arena_bytes, void *stre
     { int dev = 0, cus = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) s->num_cus = cus; }
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_tbl), tbl, sizeof(tbl));
     if (e != hipSuccess) { delete s; return fail_hip(e, "hipMemcpyToSymbol(c_tbl)"); }
-    if (qa_sch_upload_table(tbl, sizeof(tbl)) != QA_OK) { delete s; return QA_E_DEVICE; }
+    if (qa_sch_upload_table(tbl, sizeof(tbl)) != QA_OK || qa_sct_upload_table(tbl, sizeof(tbl)) != QA_OK) { delete s; return QA_E_DEVICE; }
     e = hipMemsetAsync(arena, 0, (size_t)s->L.total, st);
     if (e != hipSuccess) { delete s; return fail_hip(e, "hipMemsetAsync(arena)"); }
     if (cfg->terrain_type == 1 && cfg->hf_ceiling) {     // "no overhang anywhere" until the caller writes the ceiling field
@@ -1649,6 +1663,7 @@ static void launch_env_step(qa_sim *s, const StepArgs &a, hipStream_t st) {
     const bool helpers = helpers_switch == 1 || (helpers_switch < 0 && blocks <= s->num_cus);
     const bool xr = s->p.xr_sums != nullptr;           // qa_set_extra_rewards: the XR instantiations
     // qa_set_self_collision_hips: the SCH instantiations, which live in qa_sim_selfcol.hip
+    if (s->sc_hips == 2) { qa_sct_launch_env_step(hf, s->lean, !hf && helpers, xr, blocks, st, a); return; }      // ... and qa_sim_selfcol_thighs.hip
     if (s->sc_hips) { qa_sch_launch_env_step(hf, s->lean, !hf && helpers, xr, blocks, st, a); return; }
 #define QA_LAUNCH_STEP(PLANE_, LEAN_, HELP_) do { \
         if (xr) hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 1>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); \
@@ -1705,6 +1720,17 @@ int qa_set_self_collision_hips(qa_sim *s, int on) {
     return QA_OK;
 }
 
+int qa_set_self_collision_thighs(qa_sim *s, int on) {
+    if (!s) return QA_E_ARG;
+    if (on && !s->cfg.self_collision) {
+        snprintf(g_err, sizeof(g_err), "qa_set_self_collision_thighs: the handle was created with self_collision = 0 (the calf-thigh rows belong to the self-collision model)");
+        return QA_E_ARG;
+    }
+    if (on) s->sc_hips = 2;
+    else if (s->sc_hips == 2) s->sc_hips = 1;
+    return QA_OK;
+}
+
 int qa_set_extra_rewards(qa_sim *s, const qa_extra_rewards *x) {
     if (!s) return QA_E_ARG;
     Ptrs &p = s->p;
@@ -1748,7 +1774,8 @@ int qa_env_physics_step(qa_sim *s, const float *actions, int32_t delay_steps, vo
     if (!s || !actions || delay_steps < 0 || delay_steps >= QA_ACTION_BUF_LEN) return QA_E_ARG;
     StepArgs a; a.c = s->cfg; a.p = s->p; a.mi = mocap_idx(s); a.actions = actions; a.delay = delay_steps; a.step = 0; a.step_ptr = nullptr; a.prof = nullptr;
     const int blocks = (s->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
-    if (s->sc_hips) qa_sch_launch_physics_step(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, a);       // the SCH instantiations (qa_sim_selfcol.hip)
+    if (s->sc_hips == 2) qa_sct_launch_physics_step(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, a);  // the SCH = 2 instantiations (qa_sim_selfcol_thighs.hip)
+    else if (s->sc_hips) qa_sch_launch_physics_step(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, a);  // the SCH instantiations (qa_sim_selfcol.hip)
     else if (s->cfg.terrain_type == 1) hipLaunchKernelGGL((qa_env_step_kernel<false, 4, 1>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 1>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
@@ -1767,7 +1794,8 @@ static int launch_simulate(qa_sim *s, const float *torques, const uint8_t *cond,
     if (!s) return QA_E_ARG;
     if (!torques) torques = s->p.torques;          // the actuation forces set last (gym keeps applying them)
     const int epb = QA_BLOCK / s->lanes, blocks = (s->cfg.num_envs + epb - 1) / epb;
-    if (s->sc_hips) qa_sch_launch_simulate(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, s->cfg, s->p, torques, cond);       // the SCH instantiations (qa_sim_selfcol.hip)
+    if (s->sc_hips == 2) qa_sct_launch_simulate(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, s->cfg, s->p, torques, cond);  // the SCH = 2 instantiations (qa_sim_selfcol_thighs.hip)
+    else if (s->sc_hips) qa_sch_launch_simulate(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, s->cfg, s->p, torques, cond);  // the SCH instantiations (qa_sim_selfcol.hip)
     else if (s->cfg.terrain_type == 1) hipLaunchKernelGGL((qa_simulate_kernel<false, 4>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, s->cfg, s->p, torques, cond);
     else hipLaunchKernelGGL((qa_simulate_kernel<true, 4>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, s->cfg, s->p, torques, cond);
     HIP_TRY(hipGetLastError());

@@ -83,6 +83,7 @@ class LeggedRobotCfg(BaseConfig):
         default_dof_drive_mode = 3
         self_collisions = 0
         qa_self_collision_hips = False     # include/qa_sim_selfcol.h: also collide each front calf with the rear hip of its side (needs self_collisions == 0)
+        qa_self_collision_thighs = False    # ... and each calf of a front / rear pair with the other leg's thigh (needs qa_self_collision_hips)
         replace_cylinder_with_capsule = True
         flip_visual_attachments = True
         density = 0.001

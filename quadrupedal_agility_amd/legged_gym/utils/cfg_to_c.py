@@ -148,6 +148,22 @@ def install_self_collision_hips(cfg, sim):
     return True
 
 
+def install_self_collision_thighs(cfg, sim):
+    """asset.qa_self_collision_thighs -> qa_set_self_collision_thighs on the engine `sim`, for the env classes of both trees: the calf-thigh rows
+    on top of the calf-hip rows, so the config must ask for those too.  Call it where install_self_collision_hips is called, after it.
+    Returns whether the feature is on."""
+    if not getattr(cfg.asset, "qa_self_collision_thighs", False):
+        return False
+    if not getattr(cfg.asset, "qa_self_collision_hips", False):
+        raise ValueError("asset.qa_self_collision_thighs needs asset.qa_self_collision_hips = True as well: the calf-thigh rows come on top of the calf-hip rows")
+    if getattr(cfg.asset, "self_collisions", 0) != 0:
+        raise ValueError("asset.qa_self_collision_thighs needs self-collision enabled (asset.self_collisions == 0): the calf-thigh rows belong to that model")
+    if not hasattr(sim, "set_self_collision_thighs"):
+        raise NotImplementedError("asset.qa_self_collision_thighs needs the HIP engine (qa_set_self_collision_thighs); this backend has no twin of it")
+    sim.set_self_collision_thighs(True)
+    return True
+
+
 class ExtraRewards:
     """What qa_set_extra_rewards (include/qa_sim_rewards.h) needs besides device buffers: `scale_dt` in _capi.EXTRA_REWARD_NAMES order,
     the two targets, dt as the fp32 step the air time advances by, and the (n, 2) scan grid (None: measured heights are 0)."""

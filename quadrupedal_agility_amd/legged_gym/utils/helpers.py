@@ -96,6 +96,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             env_cfg.terrain.curriculum = True
         if getattr(args, "self_collision_hips", False):
             env_cfg.asset.qa_self_collision_hips = True
+        if getattr(args, "self_collision_thighs", False):
+            env_cfg.asset.qa_self_collision_thighs = True
         if getattr(args, "no_mocap_init", False):
             env_cfg.env.mocap_state_init = False
         for item in getattr(args, "reward_scale", None) or []:
@@ -154,6 +156,7 @@ def get_args(argv=None):
     p.add_argument("--terrain", type=str, default=None, help="override terrain.mesh_type: plane | heightfield | trimesh")
     p.add_argument("--terrain_curriculum", action="store_true", help="terrain.curriculum = True: resetting envs move between the course's difficulty rows (heightfield | trimesh)")
     p.add_argument("--self_collision_hips", action="store_true", help="asset.qa_self_collision_hips = True: a front calf collides with the rear hip of its side (a hip contact ends the episode, as in the reference)")
+    p.add_argument("--self_collision_thighs", action="store_true", help="asset.qa_self_collision_thighs = True: each calf of a front / rear pair of legs collides with the other leg's thigh (the collision penalty counts it; pass --self_collision_hips too)")
     p.add_argument("--reward_scale", action="append", default=[], metavar="NAME=VALUE",
                    help="rewards.scales.NAME = VALUE (repeatable), e.g. lin_vel_z=-2.0 feet_air_time=1.0: any term the fused step computes")
     p.add_argument("--no_amp", action="store_true", help="disable the discriminator (BASELINE config 2)")

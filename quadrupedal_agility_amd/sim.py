@@ -111,6 +111,16 @@ class QaSim:
         it selects other kernels at launch time, so call it before a rollout is recorded."""
         self.api.call("set_self_collision_hips", self.h, int(bool(on)))
         self.self_collision_hips = bool(on)
+        self.self_collision_thighs = False                 # the C side drops the calf-thigh rows with the level it sets
+
+    def set_self_collision_thighs(self, on):
+        """qa_set_self_collision_thighs (include/qa_sim_selfcol.h): on top of the calf-hip rows, each calf of a front / rear pair of legs collides
+        with the other leg's thigh; the force lands on CONTACT_FORCES' calf and THIGH rows (the collision penalty counts it, no termination).
+        Switching it on switches the calf-hip rows on too; switching it off leaves them on.  Call it before a rollout is recorded."""
+        self.api.call("set_self_collision_thighs", self.h, int(bool(on)))
+        self.self_collision_thighs = bool(on)
+        if on:
+            self.self_collision_hips = True
 
     def step_dev(self, actions, delay, step_counter):
         """qa_env_step_dev: the step counter lives in device memory (graph-replayable)."""

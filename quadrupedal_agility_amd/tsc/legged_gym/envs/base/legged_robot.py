@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from quadrupedal_agility_amd import _capi, go2_limits
-from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import class_to_dict, install_self_collision_hips
+from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import class_to_dict, install_self_collision_hips, install_self_collision_thighs
 from quadrupedal_agility_amd.tsc.legged_gym.obstacle_curriculum import ObstacleCurriculum
 from quadrupedal_agility_amd.tsc.legged_gym.task_level import TaskLevelBookkeeping
 from quadrupedal_agility_amd.tsc.legged_gym.utils.obstacle import Obstacle
@@ -110,6 +110,7 @@ class LeggedRobot:
         self.sim = backend
         self.device = str(backend.device)
         self.self_collision_hips = install_self_collision_hips(cfg, self.sim)      # before anything records a rollout: it selects the kernels
+        self.self_collision_thighs = install_self_collision_thighs(cfg, self.sim)
         dev = self.device
         t = self.sim.t
         # (a copy: on a CPU backend from_numpy would alias the course's own array, and the obstacle curriculum writes into this tensor)

@@ -147,6 +147,7 @@ class LeggedRobotCfg(BaseConfig):
         fix_base_link = False
         self_collisions = 0
         qa_self_collision_hips = False     # include/qa_sim_selfcol.h: also collide each front calf with the rear hip of its side (needs self_collisions == 0)
+        qa_self_collision_thighs = False    # ... and each calf of a front / rear pair with the other leg's thigh (needs qa_self_collision_hips)
 
     class domain_rand:
         randomize_friction, friction_range = True, [0.6, 2.0]

@@ -148,7 +148,16 @@ def pair_gaps(dof_pos):
                         continue
                     kx, ky = sorted([x, y])
                     put(f"{kx} - {ky}, {tag}", body_gap(c[a + "_" + x], c[b + "_" + y]))
+    out.update(calf_thigh_relation_gaps(dof_pos))          # the calf-thigh class again, per ordered relation (which relations carry it: DESIGN 3.4)
     return out
+
+
+def calf_thigh_relation_gaps(dof_pos):
+    """{"calf - thigh, FL->RL": (N,) gap, ...}: the calf-thigh class per ORDERED (calf leg -> thigh leg) relation, all twelve of them, from
+    joint angles alone (a pure function of dof_pos (N, 12)).  The aggregate keys of pair_gaps ("calf - thigh, neighbouring legs" /
+    "... diagonal legs") are the minima of these over the relations of their tag."""
+    c = capsules(dof_pos)
+    return {f"calf - thigh, {a}->{b}": body_gap(c[a + "_calf"], c[b + "_thigh"]) for a in LEGS for b in LEGS if a != b}
 
 
 def train_behaviour_policy(iters, seed):
