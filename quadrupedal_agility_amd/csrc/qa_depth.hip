@@ -13,7 +13,9 @@
 #include <stdio.h>
 
 #include "../../include/qa_sim.h"
+#include "../../include/qa_tsc_depth_obstacles.h"
 #include "qa_device.h"
+#include "qa_obst_surface.h"
 
 extern thread_local char qa_err_buf[512];
 
@@ -49,14 +51,53 @@ __device__ __forceinline__ float tri_height(const int16_t *__restrict__ m, int c
     return h00 + a * (hm - h00) + b * (h11 - hm);
 }
 
-__global__ void __launch_bounds__(256) qa_tsc_depth_kernel(DepthArgs a) {
+
+// ART (qa_tsc_depth_update_obstacles): the env's three articulated obstacles are rendered in their current joint state.  ART = 0 is the
+// kernel as it was.  The ART = 1 kernel runs AFTER it, on the same stream, and renders again only the pixels whose ray passes over a
+// footprint's bounding box within the far clip: it overwrites the value the first launch pushed into the ring.  A ray that passes over
+// no box takes no sample inside a footprint, so the static march is its march -- and keeping the first launch's value, instead of
+// recomputing it, is what makes records that cover nothing (kind 0, out of view) give the static image bit for bit: two instantiations of
+// one source are two compilations, and they do not contract the same multiply-adds.
+// The kernel's arguments grow by the two tensors, its LDS by the env's records (36 floats, qa_obst_surface.h) and the footprints' boxes
+// (12 floats); every floor / ceiling lookup of its march goes through cover_at / floor_at / ceiling_at.
+template <bool ART> struct KernelArgs : DepthArgs {};
+template <> struct KernelArgs<true> : DepthArgs { const float *obst_desc, *obst_state; };
+
+template <bool ART> __device__ __forceinline__ qa_os_cover cover_at(const float *rec, float x, float y) {
+    if constexpr (ART) return qa_os_classify(rec, x, y);
+    else return qa_os_cover{};
+}
+template <bool ART> __device__ __forceinline__ float floor_at(const qa_os_cover &cv, const int16_t *__restrict__ m, int cols, float vs, const Cell &c) {
+    bool exists;
+    const float h = tri_height(m, cols, vs, c, exists);
+    if constexpr (ART) return qa_os_floor(&cv, h);
+    else return h;
+}
+template <bool ART> __device__ __forceinline__ float ceiling_at(const qa_os_cover &cv, const int16_t *__restrict__ m, int cols, float vs, const Cell &c, bool &exists) {
+    const float h = tri_height(m, cols, vs, c, exists);
+    if constexpr (ART) return qa_os_ceiling(&cv, h);
+    else return h;
+}
+
+template <bool ART> __global__ void __launch_bounds__(256) qa_tsc_depth_kernel(KernelArgs<ART> a) {
     const qa_tsc_depth_cfg &c = a.c;
     // workgroup id -> (env, pixel tile).  Consecutive workgroup ids go round-robin over the 8 XCDs, each with its own L2: id = 8 s + x
     // runs on XCD x, so env = 8 (s / tiles) + x keeps all tiles of one env -- which walk the same ~100 KB of the two maps -- on ONE L2
     const int npix = a.wc * a.hc, tiles = a.tiles;
     const int x = blockIdx.x & 7, sl = blockIdx.x >> 3;
     const int64_t e = (int64_t)(sl / tiles) * 8 + x;
-    if (e >= c.num_envs) return;
+    if (e >= c.num_envs) return;                                        // (workgroup-uniform: no lane of this workgroup reaches the barrier below)
+    __shared__ float s_ob[ART ? 48 : 1];                                // [3 records of 12 | 3 boxes of 4]
+    if constexpr (ART) {
+        // every pixel of a workgroup belongs to one env: its records are staged once, by the first 36 threads, its boxes by the next three;
+        // the lanes of a partial tile (p >= npix) take part in the barrier and leave after it
+        const float *od = a.obst_desc + e * (QA_OS_SLOTS * 8), *os = a.obst_state + e * (QA_OS_SLOTS * 4);
+        const int tid = threadIdx.x;
+        if (tid < QA_OS_SLOTS * QA_OS_RECORD) s_ob[tid] = qa_os_record_float(od, os, tid / QA_OS_RECORD, tid % QA_OS_RECORD);
+        else if (tid < QA_OS_SLOTS * QA_OS_RECORD + QA_OS_SLOTS) qa_os_box(od, tid - QA_OS_SLOTS * QA_OS_RECORD, s_ob + QA_OS_SLOTS * QA_OS_RECORD + 4 * (tid - QA_OS_SLOTS * QA_OS_RECORD));
+        __syncthreads();
+    }
+    const float *boxes = s_ob + (ART ? QA_OS_SLOTS * QA_OS_RECORD : 0);
     const int p = (sl % tiles) * 256 + threadIdx.x;
     if (p >= npix) return;
     const float *rs = a.io.root_states + e * 13;
@@ -86,26 +127,33 @@ __global__ void __launch_bounds__(256) qa_tsc_depth_kernel(DepthArgs a) {
     const int S = c.coarse_log2, ccols = ((cols - 2) >> S) + 1, crows = ((rows - 2) >> S) + 1;
     const float block = (float)(1 << S) * hs;
     const float idx = d[0] != 0.f ? 1.0f / d[0] : 0.f, idy = d[1] != 0.f ? 1.0f / d[1] : 0.f;
+    if constexpr (ART) {
+        // a ray that passes over no footprint's box within the far clip keeps the pixel the static launch wrote
+        if (!qa_os_ray_meets_boxes(boxes, o[0], o[1], d[0], d[1], idx, idy, far)) return;
+    }
     int seen_cx = -1, seen_cy = -1;                                     // the block that last refused a skip: not asked again while inside it
     int blk_cx = -1, blk_cy = -1; bool blk_roof = true;                 // the block of the current sample: has it any ceiling sample at all?
-    bool ex_prev = false, ex = false, dummy;
+    bool ex_prev = false, ex = false;
     float t_prev = 0.f, hit = far;
     Cell c0 = cell_of(o[0], o[1], border, a.inv_hs, rows, cols);
-    float g_prev = o[2] - tri_height(hm, cols, vs, c0, dummy);
-    float h_prev = cm ? o[2] - tri_height(cm, cols, vs, c0, ex_prev) : 0.f;
+    const qa_os_cover cv0 = cover_at<ART>(s_ob, o[0], o[1]);
+    float g_prev = o[2] - floor_at<ART>(cv0, hm, cols, vs, c0);
+    float h_prev = cm ? o[2] - ceiling_at<ART>(cv0, cm, cols, vs, c0, ex_prev) : 0.f;
     if (g_prev < 0.f) hit = 0.f;
     else for (int k = 1; k <= nsteps; ++k) {
         const float t = fminf((float)k * dt, far);
         const float x = o[0] + t * d[0], y = o[1] + t * d[1], z = o[2] + t * d[2];
         const Cell ck = cell_of(x, y, border, a.inv_hs, rows, cols);
-        const float g = z - tri_height(hm, cols, vs, ck, dummy);
+        const qa_os_cover cvk = cover_at<ART>(s_ob, x, y);
+        const float g = z - floor_at<ART>(cvk, hm, cols, vs, ck);
         float h = 0.f, best = 1e30f;
         if (g < 0.f) {                      // the floor was crossed in (t_prev, t]: QA_TSC_DEPTH_BISECT halvings, then linear interpolation
             float lo = t_prev, hi = t, flo = g_prev, fhi = g;
             for (int b = 0; b < QA_TSC_DEPTH_BISECT; ++b) {
                 const float tm = 0.5f * (lo + hi);
-                const Cell cb = cell_of(o[0] + tm * d[0], o[1] + tm * d[1], border, a.inv_hs, rows, cols);
-                const float fm = o[2] + tm * d[2] - tri_height(hm, cols, vs, cb, dummy);
+                const float xm = o[0] + tm * d[0], ym = o[1] + tm * d[1];
+                const Cell cb = cell_of(xm, ym, border, a.inv_hs, rows, cols);
+                const float fm = o[2] + tm * d[2] - floor_at<ART>(cover_at<ART>(s_ob, xm, ym), hm, cols, vs, cb);
                 if (fm < 0.f) { hi = tm; fhi = fm; } else { lo = tm; flo = fm; }
             }
             best = lo + (hi - lo) * flo / (flo - fhi);
@@ -114,13 +162,14 @@ __global__ void __launch_bounds__(256) qa_tsc_depth_kernel(DepthArgs a) {
         if (cce && (cx != blk_cx || cy != blk_cy)) { blk_cx = cx; blk_cy = cy; blk_roof = cce[cx * ccols + cy] != QA_NO_CEILING; }
         ex = false;
         if (cm && blk_roof) {               // a block without a single ceiling sample has no ceiling triangle: ex stays false
-            h = z - tri_height(cm, cols, vs, ck, ex);
+            h = z - ceiling_at<ART>(cvk, cm, cols, vs, ck, ex);
             if (ex && ex_prev && ((h_prev < 0.f) != (h < 0.f))) {
                 float lo = t_prev, hi = t, flo = h_prev, fhi = h;
                 for (int b = 0; b < QA_TSC_DEPTH_BISECT; ++b) {
                     const float tm = 0.5f * (lo + hi); bool exm;
-                    const Cell cb = cell_of(o[0] + tm * d[0], o[1] + tm * d[1], border, a.inv_hs, rows, cols);
-                    const float fm = o[2] + tm * d[2] - tri_height(cm, cols, vs, cb, exm);
+                    const float xm = o[0] + tm * d[0], ym = o[1] + tm * d[1];
+                    const Cell cb = cell_of(xm, ym, border, a.inv_hs, rows, cols);
+                    const float fm = o[2] + tm * d[2] - ceiling_at<ART>(cover_at<ART>(s_ob, xm, ym), cm, cols, vs, cb, exm);
                     if (!exm) break;                                     // a hole in the shell inside the bracket: keep the bracket
                     if ((fm < 0.f) == (flo < 0.f)) { lo = tm; flo = fm; } else { hi = tm; fhi = fm; }
                 }
@@ -138,15 +187,22 @@ __global__ void __launch_bounds__(256) qa_tsc_depth_kernel(DepthArgs a) {
             const float tx = d[0] != 0.f ? (bx - o[0]) * idx : 1e30f, ty = d[1] != 0.f ? (by - o[1]) * idy : 1e30f;
             const float t_exit = fminf(fminf(tx, ty), far);
             const int kl = min((int)floorf((t_exit - 1e-4f) / dt), nsteps - 1);   // the last lattice sample safely inside (the final, clamped one is always marched)
-            if (kl > k + 1) {
+            // ART: the coarse maps bound the static map only -- neither the plank (0.51 m against the A-frame's 0.26 m) nor a bar raised by
+            // q > 0.  A block that overlaps a footprint's box is never skipped, so no joint position enters a bound.
+            bool clear = true;
+            if constexpr (ART) clear = !qa_os_boxes_overlap(boxes, cx == 0 ? -1e30f : x0, cx == crows - 1 ? 1e30f : x0 + block,
+                                                            cy == 0 ? -1e30f : y0, cy == ccols - 1 ? 1e30f : y0 + block);
+            if (kl > k + 1 && clear) {
                 const float tl = (float)kl * dt, zl = o[2] + tl * d[2];
                 const float hmax = vs * (float)cfl[cx * ccols + cy];
                 const float cmin = (cm && cce) ? vs * (float)cce[cx * ccols + cy] : 1e30f;
                 if (fminf(z, zl) > hmax + 1e-3f && fmaxf(z, zl) < cmin - 1e-3f) {
-                    const Cell cl = cell_of(o[0] + tl * d[0], o[1] + tl * d[1], border, a.inv_hs, rows, cols);
+                    const float xl = o[0] + tl * d[0], yl = o[1] + tl * d[1];
+                    const Cell cl = cell_of(xl, yl, border, a.inv_hs, rows, cols);
                     if ((cl.ix >> S) == cx && (cl.iy >> S) == cy) {          // rounding never moves it out, but the jump is only taken if it did not
-                        t_prev = tl; g_prev = zl - tri_height(hm, cols, vs, cl, dummy);
-                        h_prev = cm ? zl - tri_height(cm, cols, vs, cl, ex_prev) : 0.f;
+                        const qa_os_cover cvl = cover_at<ART>(s_ob, xl, yl);
+                        t_prev = tl; g_prev = zl - floor_at<ART>(cvl, hm, cols, vs, cl);
+                        h_prev = cm ? zl - ceiling_at<ART>(cvl, cm, cols, vs, cl, ex_prev) : 0.f;
                         k = kl; seen_cx = -1;                                // the block after this one is asked afresh
                     }
                 }
@@ -167,6 +223,8 @@ __global__ void __launch_bounds__(256) qa_tsc_depth_kernel(DepthArgs a) {
     float *buf = a.io.depth_buffer + e * c.buffer_len * (int64_t)npix + p;
     if (a.io.episode_length[e] <= 1) {
         for (int s = 0; s < c.buffer_len; ++s) buf[(int64_t)s * npix] = v;
+    } else if constexpr (ART) {
+        buf[(int64_t)(c.buffer_len - 1) * npix] = v;                      // (the static launch has shifted the ring)
     } else {
         for (int s = 0; s + 1 < c.buffer_len; ++s) buf[(int64_t)s * npix] = buf[(int64_t)(s + 1) * npix];
         buf[(int64_t)(c.buffer_len - 1) * npix] = v;
@@ -175,16 +233,21 @@ __global__ void __launch_bounds__(256) qa_tsc_depth_kernel(DepthArgs a) {
 
 }  // namespace
 
-extern "C" int qa_tsc_depth_update(const qa_tsc_depth_cfg *cfg, const qa_tsc_depth_io *io, void *stream) {
-    if (!cfg || !io) { snprintf(qa_err_buf, sizeof(qa_err_buf), "qa_tsc_depth_update: null argument"); return QA_E_ARG; }
+// both entry points: the static launch and, with `obst`, the obstacle launch behind it; `fn` names the caller in the error text
+static int depth_launch(const char *fn, const qa_tsc_depth_cfg *cfg, const qa_tsc_depth_io *io, const qa_tsc_depth_obstacles *obst, void *stream) {
+    if (!cfg || !io) { snprintf(qa_err_buf, sizeof(qa_err_buf), "%s: null argument", fn); return QA_E_ARG; }
     if (!io->root_states || !io->camera_pitch || !io->height_samples || !io->episode_length || !io->depth_buffer) {
-        snprintf(qa_err_buf, sizeof(qa_err_buf), "qa_tsc_depth_update: a required io pointer is null"); return QA_E_ARG;
+        snprintf(qa_err_buf, sizeof(qa_err_buf), "%s: a required io pointer is null", fn); return QA_E_ARG;
     }
+    if (obst && (obst->obst_desc == nullptr) != (obst->obst_state == nullptr)) {
+        snprintf(qa_err_buf, sizeof(qa_err_buf), "%s: obst_desc and obst_state must be given together (one of them is null)", fn); return QA_E_ARG;
+    }
+    const bool art = obst && obst->obst_desc;
     DepthArgs a; a.c = *cfg; a.io = *io;
     a.wc = cfg->width - cfg->crop_left - cfg->crop_right; a.hc = cfg->height - cfg->crop_top - cfg->crop_bottom;
     if (cfg->num_envs <= 0 || cfg->num_envs > (1 << 22) || a.wc <= 0 || a.hc <= 0 || cfg->buffer_len < 1 || cfg->map_rows < 2 || cfg->map_cols < 2 || !(cfg->horizontal_scale > 0.f) ||
         cfg->coarse_log2 < 0 || cfg->coarse_log2 > 6 || !(cfg->far_clip > cfg->near_clip) || !(cfg->horizontal_fov_deg > 0.f && cfg->horizontal_fov_deg < 180.f)) {
-        snprintf(qa_err_buf, sizeof(qa_err_buf), "qa_tsc_depth_update: inconsistent configuration"); return QA_E_ARG;
+        snprintf(qa_err_buf, sizeof(qa_err_buf), "%s: inconsistent configuration", fn); return QA_E_ARG;
     }
     a.tan_h = (float)tan((double)cfg->horizontal_fov_deg * 3.14159265358979323846 / 360.0);
     a.tan_v = (float)(tan((double)cfg->horizontal_fov_deg * 3.14159265358979323846 / 360.0) * cfg->height / cfg->width);
@@ -192,8 +255,24 @@ extern "C" int qa_tsc_depth_update(const qa_tsc_depth_cfg *cfg, const qa_tsc_dep
     const int npix = a.wc * a.hc;
     a.tiles = (npix + 255) / 256;
     const int64_t groups = (cfg->num_envs + 7) / 8 * 8 * a.tiles;          // envs rounded up to the 8 XCDs
-    hipLaunchKernelGGL(qa_tsc_depth_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, a);
+    {
+        KernelArgs<false> ka; static_cast<DepthArgs &>(ka) = a;
+        hipLaunchKernelGGL(qa_tsc_depth_kernel<false>, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, ka);
+    }
+    if (art) {          // behind it on the same stream: the pixels whose ray passes over a footprint's box are rendered again, obstacles in
+        KernelArgs<true> ka; static_cast<DepthArgs &>(ka) = a; ka.obst_desc = obst->obst_desc; ka.obst_state = obst->obst_state;
+        hipLaunchKernelGGL(qa_tsc_depth_kernel<true>, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, ka);
+    }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(qa_err_buf, sizeof(qa_err_buf), "qa_tsc_depth_update: %s", hipGetErrorString(e)); return QA_E_DEVICE; }
+    if (e != hipSuccess) { snprintf(qa_err_buf, sizeof(qa_err_buf), "%s: %s", fn, hipGetErrorString(e)); return QA_E_DEVICE; }
     return QA_OK;
+}
+
+extern "C" int qa_tsc_depth_update(const qa_tsc_depth_cfg *cfg, const qa_tsc_depth_io *io, void *stream) {
+    return depth_launch("qa_tsc_depth_update", cfg, io, nullptr, stream);
+}
+
+// include/qa_tsc_depth_obstacles.h
+extern "C" int qa_tsc_depth_update_obstacles(const qa_tsc_depth_cfg *cfg, const qa_tsc_depth_io *io, const qa_tsc_depth_obstacles *obst, void *stream) {
+    return depth_launch("qa_tsc_depth_update_obstacles", cfg, io, obst, stream);
 }

@@ -174,8 +174,15 @@ class LeggedRobot:
             lo, hi = cfg.depth.angle
             n_glob, off = int(self.qcfg.num_envs_global) or self.num_envs, int(self.qcfg.env_id_offset)
             ang = np.random.default_rng([seed, 0xCA3E]).uniform(lo, hi, n_glob)[off:off + self.num_envs]
+            # depth.qa_articulated (include/qa_tsc_depth_obstacles.h): the ray-cast reads the engine's live obstacle tensors, so the image shows
+            # the see-saw, bar and tyre where the physics has them.  Chosen here, before anything records a rollout: a recording bakes the launch in
+            live = {}
+            if getattr(cfg.depth, "qa_articulated", False):
+                if not self.articulated:
+                    raise ValueError("depth.qa_articulated needs obstacle.articulated = True: without the bodies there is no joint state to render")
+                live = dict(obst_desc=t["OBST_DESC"], obst_state=self.obst_state)
             self.bk.init_depth(self.height_samples, torch.as_tensor(self.obstacle.ceiling_raw, dtype=torch.int16),
-                               torch.as_tensor(np.radians(ang), dtype=torch.float32), seed=seed, env_id_offset=off)
+                               torch.as_tensor(np.radians(ang), dtype=torch.float32), seed=seed, env_id_offset=off, **live)
         # ---- obstacle curriculum (:917-957): armed on the teacher's env only.  A camera env keeps the as-built course, as the reference's
         # vision flows do (learn_vision and play.py switch the flag off): the depth ray-cast's maps and their coarse structure never see a raise
         if cfg.obstacle.curriculum:

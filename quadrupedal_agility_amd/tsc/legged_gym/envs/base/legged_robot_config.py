@@ -58,6 +58,7 @@ class LeggedRobotCfg(BaseConfig):
         buffer_len = 2
         near_clip, far_clip, depth_noise = 0.3, 4, 0.05
         scale, invert = 1, True
+        qa_articulated = False     # include/qa_tsc_depth_obstacles.h: render see-saw, bar and tyre in their current joint state (needs obstacle.articulated)
 
     class normalization:
         class obs_scales:

@@ -269,10 +269,23 @@ class TaskLevelBookkeeping:
         self.api.launch("tsc_observations", C.byref(self._ocfg), C.byref(io), on=self.device)
         return self.obs_buf
 
-    def init_depth(self, height_samples, ceiling_samples, camera_pitch, seed=1, env_id_offset=0):
+    def init_depth(self, height_samples, ceiling_samples, camera_pitch, seed=1, env_id_offset=0, obst_desc=None, obst_state=None):
         """The depth camera of attach_camera (:1203-1226) and the `depth` config block: one camera per env on the trunk, pitched
-        down by `camera_pitch` (N) radians; `depth_buffer` (N, buffer_len, 58, 87) is the reference's ring."""
+        down by `camera_pitch` (N) radians; `depth_buffer` (N, buffer_len, 58, 87) is the reference's ring.
+        `obst_desc` (N,3,8) / `obst_state` (N,3,4): the engine's LIVE QA_T_OBST_DESC / QA_T_OBST_STATE tensors (depth.qa_articulated,
+        include/qa_tsc_depth_obstacles.h) -- kept by reference, not copied: every render reads the joints' current state."""
         d, dev, n = self.cfg.depth, self.device, self.num_envs
+        if (obst_desc is None) != (obst_state is None):
+            raise ValueError("init_depth: obst_desc and obst_state go together")
+        self._depth_obst = None
+        if obst_desc is not None:
+            if not hasattr(self.lib, self.api.prefix + "tsc_depth_update_obstacles"):
+                raise NotImplementedError("depth.qa_articulated needs the HIP library (qa_tsc_depth_update_obstacles); this backend has no "
+                                          f"{self.api.prefix}tsc_depth_update_obstacles: the camera would show the static map")
+            for name, t, shape in (("obst_desc", obst_desc, (n, 3, 8)), ("obst_state", obst_state, (n, 3, 4))):
+                if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device.type != dev.type or not t.is_contiguous():
+                    raise ValueError(f"init_depth: {name} must be a contiguous float32 {shape} tensor on {dev}")
+            self._depth_obst = (obst_desc, obst_state)
         self._depth_maps = (height_samples.to(dev, torch.int16).contiguous(),
                             ceiling_samples.to(dev, torch.int16).contiguous() if ceiling_samples is not None else None)
         self.camera_pitch = camera_pitch.to(dev, torch.float32).contiguous()
@@ -308,7 +321,11 @@ class TaskLevelBookkeeping:
             io.step_dev = step.data_ptr()
         else:
             self._dcfg.step = int(step)
-        self.api.launch("tsc_depth_update", C.byref(self._dcfg), C.byref(io), on=self.device)
+        if self._depth_obst is not None:
+            ob = _capi.QaTscDepthObstacles(self._depth_obst[0].data_ptr(), self._depth_obst[1].data_ptr())
+            self.api.launch("tsc_depth_update_obstacles", C.byref(self._dcfg), C.byref(io), C.byref(ob), on=self.device)
+        else:
+            self.api.launch("tsc_depth_update", C.byref(self._dcfg), C.byref(io), on=self.device)
         return self.depth_buffer
 
     def get_observations(self):
