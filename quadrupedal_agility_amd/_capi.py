@@ -51,6 +51,9 @@ DTYPE_F32, DTYPE_I64, DTYPE_U8, DTYPE_I32, DTYPE_I16, DTYPE_F64 = 0, 1, 2, 3, 4,
 BODY_NAMES = ["base", "Head_upper", "Head_lower"] + [
     f"{l}_{p}" for l in ("FL", "FR", "RL", "RR") for p in ("hip", "thigh", "calf", "foot")]
 DOF_NAMES = [f"{l}_{p}_joint" for l in ("FL", "FR", "RL", "RR") for p in ("hip", "thigh", "calf")]
+# include/qa_sim_reset.h (QA_BC_*): the body classes qa_set_contact_sets' masks are built from, and the kernels' defaults
+BODY_CLASS_BITS = {"base": 1, "hip": 2, "thigh": 4, "calf": 8, "foot": 16}
+DEFAULT_TERMINATION_MASK, DEFAULT_PENALISED_MASK = 1 | 2, 4 | 8
 
 
 class QaConfig(C.Structure):
@@ -252,6 +255,9 @@ def bind_extensions(lib, prefix="qa_"):
     # include/qa_sim_selfcol.h
     f = getattr(lib, prefix + "set_self_collision_hips"); f.argtypes = [C.c_void_p, C.c_int]; f.restype = C.c_int
     f = getattr(lib, prefix + "set_self_collision_thighs"); f.argtypes = [C.c_void_p, C.c_int]; f.restype = C.c_int
+    # include/qa_sim_reset.h
+    f = getattr(lib, prefix + "set_recovery_init"); f.argtypes = [C.c_void_p, C.c_float]; f.restype = C.c_int
+    f = getattr(lib, prefix + "set_contact_sets"); f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]; f.restype = C.c_int
     # include/qa_tsc_rewards.h
     f = getattr(lib, prefix + "tsc_goal_step_rewards"); f.argtypes = [C.POINTER(QaTscGoalCfg), C.POINTER(QaTscGoalIo), C.POINTER(QaTscExtraRewards), C.c_void_p]; f.restype = C.c_int
     # include/qa_tsc_depth_obstacles.h
@@ -423,7 +429,7 @@ ABI_SYMBOLS = ["arena_bytes", "create", "destroy", "tensor_info", "env_step", "e
 # include/qa_sim_curriculum.h, include/qa_tsc_curriculum.h, include/qa_sim_rewards.h, include/qa_sim_selfcol.h, include/qa_tsc_rewards.h,
 # include/qa_tsc_depth_obstacles.h (bind_extensions)
 EXTENSION_SYMBOLS = ["set_terrain_curriculum", "tsc_obstacle_curriculum", "set_extra_rewards", "set_self_collision_hips", "set_self_collision_thighs", "tsc_goal_step_rewards",
-                     "tsc_depth_update_obstacles"]
+                     "tsc_depth_update_obstacles", "set_recovery_init", "set_contact_sets"]
 
 _LIB = None
 # QA_LIB: another build of the SAME library (A/B measurements of a kernel variant, tools/r5_call.sh); there is still no fallback -- a missing file raises

@@ -168,6 +168,6 @@ QA_DEV F4 rng4(uint64_t seed, uint32_t env, int64_t step, int stream, int block)
     return f;
 }
 enum { RS_INIT_BUCKET = 1, RS_INIT_FRICTION = 2, RS_INIT_MASS = 3, RS_INIT_MOTOR = 4,
-       RS_NOISE = 8, RS_CMD = 9, RS_CMD_RESET = 10, RS_PUSH = 11, RS_RESET = 12, RS_TERRAIN_LEVEL = 13 };
+       RS_NOISE = 8, RS_CMD = 9, RS_CMD_RESET = 10, RS_PUSH = 11, RS_RESET = 12, RS_TERRAIN_LEVEL = 13, RS_RECOVERY = 14 };
 
 QA_DEV float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }

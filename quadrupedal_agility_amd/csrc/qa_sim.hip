@@ -20,6 +20,7 @@
 #include "../../include/qa_sim_curriculum.h"
 #include "../../include/qa_sim_rewards.h"
 #include "../../include/qa_sim_selfcol.h"
+#include "../../include/qa_sim_reset.h"
 #include "qa_go2_model.h"
 #include "qa_physics.h"
 #include "qa_rewards.h"
@@ -124,6 +125,9 @@ struct Ptrs {
     const float *xr_scan;
     int32_t xr_scan_n;
     float xr_scale[QA_NUM_EXTRA_REWARDS], xr_target, xr_max_force, xr_dt;
+    // qa_set_recovery_init, qa_set_contact_sets (include/qa_sim_reset.h): 0 = no recovery resets; the QA_BC_* classes that terminate / are penalised
+    float rec_prob;
+    uint32_t term_mask, pen_mask;
 };
 
 struct qa_sim {
@@ -267,6 +271,38 @@ __device__ __forceinline__ void update_terrain_level(const qa_config &c, const P
     }
 }
 
+// _reset_dofs_rec / _reset_root_states_rec (legged_robot.py:636-658) of one env by its quad, include/qa_sim_reset.h: 33 uniforms of stream
+// RS_RECOVERY, blocks 1..9, in the reference's call order; every product and sum rounded on its own, as torch_rand_float's (hi - lo) * u + lo is
+// (fp contraction is off in here: the compiler would fuse them otherwise).  Each block is consumed as it is drawn, so no 36-value array is live.
+__device__ __forceinline__ void recovery_pose(const qa_config &c, int env, int leg, int64_t step, float ox, float oy, float oz, EnvState &st) {
+#pragma clang fp contract(off)
+    const uint32_t ge = env + c.env_id_offset;
+    float f[3] = {0.f, 0.f, 0.f}, v[3] = {0.f, 0.f, 0.f};          // this leg's joint factors u[3 leg + k] and velocities u[12 + 3 leg + k]
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        const F4 t = rng4(c.seed, ge, step, RS_RECOVERY, 1 + b), w = rng4(c.seed, ge, step, RS_RECOVERY, 4 + b);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int j = 4 * b + i;                                // compile-time joint index: leg j / 3, joint j % 3 of it
+            const float m = (leg == j / 3) ? 1.0f : 0.0f;           // blended arithmetically on the lane's leg (u is finite: m * u is u or 0)
+            f[j % 3] += m * t.v[i]; v[j % 3] += m * w.v[i];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        st.q[k] = c.default_dof_pos[k] * (1.5f * f[k] + 0.5f);         // the default pose is the same for every leg; not clamped
+        st.qd[k] = 2.0f * v[k] - 1.0f;
+    }
+    const F4 a = rng4(c.seed, ge, step, RS_RECOVERY, 7), b = rng4(c.seed, ge, step, RS_RECOVERY, 8), e = rng4(c.seed, ge, step, RS_RECOVERY, 9);
+    st.vw = v3(a.v[0] - 0.5f, a.v[1] - 0.5f, a.v[2] - 0.5f);
+    st.ww = v3(a.v[3] - 0.5f, b.v[0] - 0.5f, b.v[1] - 0.5f);
+    const float roll = 6.28f * b.v[2] - 3.14f, pitch = 6.28f * b.v[3] - 3.14f, yaw = 6.28f * e.v[0] - 3.14f;
+    // sinf and cosf apart: sincosf returns the cosine through a pointer to private memory, 8 more bytes of scratch per lane in every step kernel
+    const float sy = sinf(yaw * 0.5f), cy = cosf(yaw * 0.5f), sr = sinf(roll * 0.5f), cr = cosf(roll * 0.5f), sp = sinf(pitch * 0.5f), cp = cosf(pitch * 0.5f);
+    st.qx = cy * sr * cp - sy * cr * sp; st.qy = cy * cr * sp + sy * sr * cp; st.qz = sy * cr * cp - cy * sr * sp; st.qw = cy * cr * cp + sy * sr * sp;
+    st.pos = v3(c.init_pos[0] + ox, c.init_pos[1] + oy, c.init_pos[2] + oz);
+}
+
 // reset of one env by its quad (legged_robot.py:178-240).  Updates st and the command/latent registers.  ORG: spawn at `org` (the
 // caller holds the origin in registers: the terrain curriculum may just have moved it) instead of at the env's ENV_ORIGINS row.
 template <bool ORG = false>
@@ -274,7 +310,10 @@ __device__ __forceinline__ void reset_env(const qa_config &c, const Ptrs &p, con
                                           EnvState &st, float cmd[5], float &eps, int &gait, const float *org = nullptr) {
     resample_commands(c, p.prior, env, step, RS_CMD_RESET, cmd, eps, gait);
     const float ox = ORG ? org[0] : p.env_origins[3 * env], oy = ORG ? org[1] : p.env_origins[3 * env + 1], oz = ORG ? org[2] : p.env_origins[3 * env + 2];
-    if (c.reset_mode == 1 && mi.on) {
+    // qa_set_recovery_init: one decision per step, the same in every lane of every launch of a job (the env word is no env id)
+    if (p.rec_prob > 0.0f && rng4(c.seed, 0xFFFFFFFFu, step, RS_RECOVERY, 0).v[0] < p.rec_prob) {
+        recovery_pose(c, env, leg, step, ox, oy, oz, st);
+    } else if (c.reset_mode == 1 && mi.on) {
         // MotionLoader.get_full_frame_batch (motion_loader.py:461-474): clip ~ MotionWeight inside the gait, time ~ U over the
         // clip's sampling range, the two bracketing frames blended (get_full_frame_at_time_batch :410-447); index arithmetic in
         // float64 as numpy does it, the blend itself in fp32 as torch does it
@@ -600,8 +639,11 @@ __device__ __forceinline__ void post_physics_phase(const qa_config &c, const Ptr
     // measured_heights (:469-470): before any reset, like the reference's callback
     const float scan_h = PLANE ? 0.0f : scan_center_height(T, st.pos, st.qz, st.qw);
     // ---- check_termination :168-176
-    int term_c = (sqrtf(dot(hip_f, hip_f)) > 1.0f) ? 1 : 0;
-    term_c = xor_<LPE>(term_c) | (sqrtf(dot(base_f, base_f)) > 1.0f ? 1 : 0);
+    // qa_set_contact_sets: the classes of p.term_mask (default base | hip) / p.pen_mask (default thigh | calf), blended on the mask bits
+    const float nhip = sqrtf(dot(hip_f, hip_f)), nthigh = sqrtf(dot(thigh_f, thigh_f)), ncalf = sqrtf(dot(calf_f, calf_f)), nbase = sqrtf(dot(base_f, base_f));
+    const uint32_t over1 = (nbase > 1.0f ? QA_BC_BASE : 0u) | (nhip > 1.0f ? QA_BC_HIP : 0u) | (nthigh > 1.0f ? QA_BC_THIGH : 0u) |
+                           (ncalf > 1.0f ? QA_BC_CALF : 0u) | (ffn > 1.0f ? QA_BC_FOOT : 0u);
+    const int term_c = xor_<LPE>((over1 & p.term_mask) != 0u ? 1 : 0);
     int timeout = (epl > c.max_episode_length) || (st.pos.z < -6.0f);
     {
         float chk = st.pos.x + st.pos.y + st.pos.z + st.qx + st.qy + st.qz + st.qw + st.vw.x + st.vw.y + st.vw.z + st.ww.x + st.ww.y + st.ww.z;
@@ -630,7 +672,10 @@ __device__ __forceinline__ void post_physics_phase(const qa_config &c, const Ptr
             s_tl += fmaxf(fabsf(tau_org[k]) - tbl[T_EFFORT + k] * c.soft_torque_limit, 0.f);
             s_tq += tau_org[k] * tau_org[k];
         }
-        float ncol = (sqrtf(dot(thigh_f, thigh_f)) > 0.1f ? 1.f : 0.f) + (sqrtf(dot(calf_f, calf_f)) > 0.1f ? 1.f : 0.f);
+        // the leg classes once per leg, the base once per env (lane 0 carries it into the sum); small integers: exact in any order
+        const uint32_t over01 = ((nbase > 0.1f && leg == 0) ? QA_BC_BASE : 0u) | (nhip > 0.1f ? QA_BC_HIP : 0u) | (nthigh > 0.1f ? QA_BC_THIGH : 0u) |
+                                (ncalf > 0.1f ? QA_BC_CALF : 0u) | (ffn > 0.1f ? QA_BC_FOOT : 0u);
+        const float ncol = (float)__popc(over01 & p.pen_mask);
         term[QA_R_ACTION_RATE] = xsum<LPE>(s_ar); term[QA_R_COLLISION] = xsum<LPE>(ncol); term[QA_R_DELTA_TORQUES] = xsum<LPE>(s_dt);
         term[QA_R_DOF_ACC] = xsum<LPE>(s_acc); term[QA_R_DOF_ERROR] = xsum<LPE>(s_err); term[QA_R_DOF_POS_LIMITS] = xsum<LPE>(s_pl);
         term[QA_R_DOF_VEL_LIMITS] = xsum<LPE>(s_vl); term[QA_R_HIP_POS] = xsum<LPE>(s_hip); term[QA_R_TORQUE_LIMITS] = xsum<LPE>(s_tl);
@@ -1534,6 +1579,7 @@ static void clear_extra_rewards(Ptrs &p) {
     for (int i = 0; i < QA_NUM_EXTRA_REWARDS; ++i) p.xr_scale[i] = 0.f;
     p.xr_target = 0.f; p.xr_max_force = 0.f; p.xr_dt = 0.f;
 }
+static void clear_reset_extension(Ptrs &p) { p.rec_prob = 0.f; p.term_mask = QA_BC_DEFAULT_TERMINATION; p.pen_mask = QA_BC_DEFAULT_PENALISED; }
 
 static void fill_ptrs(qa_sim *s) {
     char *a = s->arena; const Layout &L = s->L; Ptrs &p = s->p;
@@ -1559,6 +1605,7 @@ static void fill_ptrs(qa_sim *s) {
     p.ticket = (int32_t *)(a + L.off[QA_T_STEP_TICKET]);
     p.terrain_levels = nullptr; p.terrain_types = nullptr; p.terrain_origins = nullptr; p.terrain_rows = p.terrain_cols = 0; p.terrain_env_length = p.terrain_episode_s = 0.f;
     clear_extra_rewards(p);
+    clear_reset_extension(p);
 }
 
 static void build_table(float *t) {
@@ -1748,6 +1795,23 @@ int qa_set_extra_rewards(qa_sim *s, const qa_extra_rewards *x) {
     p.xr_scan = x->scan_offsets; p.xr_scan_n = x->num_scan_points;
     for (int i = 0; i < QA_NUM_EXTRA_REWARDS; ++i) p.xr_scale[i] = x->scale_dt[i];
     p.xr_target = x->base_height_target; p.xr_max_force = x->max_contact_force; p.xr_dt = x->step_dt;
+    return QA_OK;
+}
+
+int qa_set_recovery_init(qa_sim *s, float prob) {
+    if (!s) return QA_E_ARG;
+    if (!(prob >= 0.0f && prob <= 1.0f)) { snprintf(g_err, sizeof(g_err), "qa_set_recovery_init: the probability must lie in [0, 1] (0 = off), got %g", (double)prob); return QA_E_ARG; }
+    s->p.rec_prob = prob;
+    return QA_OK;
+}
+
+int qa_set_contact_sets(qa_sim *s, uint32_t termination_mask, uint32_t penalised_mask) {
+    if (!s) return QA_E_ARG;
+    if ((termination_mask | penalised_mask) & ~QA_BC_ALL) {
+        snprintf(g_err, sizeof(g_err), "qa_set_contact_sets: masks are built from QA_BC_BASE .. QA_BC_FOOT (0x%x), got 0x%x / 0x%x", QA_BC_ALL, termination_mask, penalised_mask);
+        return QA_E_ARG;
+    }
+    s->p.term_mask = termination_mask; s->p.pen_mask = penalised_mask;
     return QA_OK;
 }
 

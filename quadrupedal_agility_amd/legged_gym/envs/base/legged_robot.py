@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from quadrupedal_agility_amd import _capi, go2_limits
-from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import class_to_dict, install_self_collision_hips, install_self_collision_thighs, make_extra_rewards, make_qa_config
+from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import (class_to_dict, install_contact_sets, install_recovery_init, install_self_collision_hips, install_self_collision_thighs,
+                                                            make_extra_rewards, make_qa_config)
 
 KEY_BODY_NAMES = ["FL_foot", "FR_foot", "RL_foot", "RR_foot"]
 
@@ -76,6 +77,8 @@ class LeggedRobot:
         self.device = str(backend.device)
         self.self_collision_hips = install_self_collision_hips(cfg, self.sim)      # before anything records a rollout: it selects the kernels
         self.self_collision_thighs = install_self_collision_thighs(cfg, self.sim)
+        self.recovery_init_prob = install_recovery_init(cfg, self.sim)            # launch arguments of the step: before anything records, too
+        self.contact_class_masks = install_contact_sets(cfg, self.sim)
         if self._mocap_table is not None:
             self.sim.set_mocap(*self._mocap_table)
         self._init_buffers()

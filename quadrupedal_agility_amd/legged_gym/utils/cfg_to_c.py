@@ -164,6 +164,61 @@ def install_self_collision_thighs(cfg, sim):
     return True
 
 
+def install_recovery_init(cfg, sim):
+    """env.recovery_init_prob -> qa_set_recovery_init (include/qa_sim_reset.h) on the engine `sim`.  As in the reference (legged_robot.py:205-214)
+    the probability is consulted only with env.mocap_state_init; without it a non-zero value is reported in one line and the feature stays
+    off.  Call it after the engine is created and before anything records a rollout.  Returns the probability in force."""
+    prob = float(getattr(cfg.env, "recovery_init_prob", 0.0))
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"env.recovery_init_prob must lie in [0, 1], got {prob}")
+    if prob == 0.0:
+        return 0.0
+    if not cfg.env.mocap_state_init:
+        print(f"env.recovery_init_prob = {prob} is ignored: recovery-pose resets are drawn only with env.mocap_state_init = True (as in the reference)")
+        return 0.0
+    if not hasattr(sim, "set_recovery_init"):
+        raise NotImplementedError("env.recovery_init_prob > 0 needs the HIP engine (qa_set_recovery_init); this backend has no twin of it")
+    sim.set_recovery_init(prob)
+    return prob
+
+
+def contact_class_mask(names, what="asset.terminate_after_contacts_on"):
+    """The reference's substring rule (legged_robot.py:1034-1039: every body whose name contains one of `names`) over _capi.BODY_NAMES, as a
+    mask of _capi.BODY_CLASS_BITS.  The kernels hold one force per class and leg, so a name must select whole classes: a name that selects
+    a Head body (no contact points in this model), part of a class, or no body at all is refused."""
+    mask = 0
+    for name in names:
+        hit = [b for b in _capi.BODY_NAMES if name in b]
+        if not hit:
+            raise NotImplementedError(f"{what}: {name!r} selects no body of the Go2 ({', '.join(_capi.BODY_NAMES)})")
+        if any(b.startswith("Head") for b in hit):
+            raise NotImplementedError(f"{what}: {name!r} selects {[b for b in hit if b.startswith('Head')]}; the Head bodies carry no contact points in this model")
+        for cls, bit in _capi.BODY_CLASS_BITS.items():
+            members = [b for b in _capi.BODY_NAMES if b == cls or b.endswith("_" + cls)]
+            sel = [b for b in members if b in hit]
+            if sel and len(sel) != len(members):
+                raise NotImplementedError(f"{what}: {name!r} selects {sel} but not the other {cls} bodies; the kernels take whole body classes "
+                                          f"({', '.join(_capi.BODY_CLASS_BITS)})")
+            if sel:
+                mask |= bit
+    return mask
+
+
+def install_contact_sets(cfg, sim):
+    """asset.terminate_after_contacts_on / asset.penalize_contacts_on -> qa_set_contact_sets (include/qa_sim_reset.h) on the engine `sim`.
+    With the Go2 defaults (base + hip / thigh + calf) nothing is called: those are what the kernels do on their own.  Call it after the engine
+    is created and before anything records a rollout.  Returns the two masks in force."""
+    term = contact_class_mask(cfg.asset.terminate_after_contacts_on, "asset.terminate_after_contacts_on")
+    pen = contact_class_mask(cfg.asset.penalize_contacts_on, "asset.penalize_contacts_on")
+    if (term, pen) == (_capi.DEFAULT_TERMINATION_MASK, _capi.DEFAULT_PENALISED_MASK):
+        return term, pen
+    if not hasattr(sim, "set_contact_sets"):
+        raise NotImplementedError("asset.terminate_after_contacts_on / penalize_contacts_on other than the Go2 defaults need the HIP engine "
+                                  "(qa_set_contact_sets); this backend ends episodes on base + hip and penalises thigh + calf")
+    sim.set_contact_sets(term, pen)
+    return term, pen
+
+
 class ExtraRewards:
     """What qa_set_extra_rewards (include/qa_sim_rewards.h) needs besides device buffers: `scale_dt` in _capi.EXTRA_REWARD_NAMES order,
     the two targets, dt as the fp32 step the air time advances by, and the (n, 2) scan grid (None: measured heights are 0)."""

@@ -100,6 +100,14 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             env_cfg.asset.qa_self_collision_thighs = True
         if getattr(args, "no_mocap_init", False):
             env_cfg.env.mocap_state_init = False
+        if getattr(args, "recovery_init_prob", None) is not None:
+            env_cfg.env.recovery_init_prob = args.recovery_init_prob
+        for flag, field in (("terminate_on", "terminate_after_contacts_on"), ("penalize_on", "penalize_contacts_on")):
+            names = getattr(args, flag, None)
+            if names:                                    # `none` alone: the empty list (no contact ends an episode / none is penalised)
+                if "none" in names and len(names) > 1:
+                    raise ValueError(f"--{flag} none stands alone: it empties the list")
+                setattr(env_cfg.asset, field, [] if names == ["none"] else list(names))
         for item in getattr(args, "reward_scale", None) or []:
             name, eq, value = item.partition("=")
             if not hasattr(env_cfg.rewards.scales, name):
@@ -161,6 +169,11 @@ def get_args(argv=None):
                    help="rewards.scales.NAME = VALUE (repeatable), e.g. lin_vel_z=-2.0 feet_air_time=1.0: any term the fused step computes")
     p.add_argument("--no_amp", action="store_true", help="disable the discriminator (BASELINE config 2)")
     p.add_argument("--no_mocap_init", action="store_true", help="reset from the default pose instead of mocap frames")
+    p.add_argument("--recovery_init_prob", type=float, metavar="P", help="env.recovery_init_prob = P: with this probability a step's resetting envs are thrown in tumbled instead of taking a mocap frame (fall recovery; needs mocap init)")
+    p.add_argument("--terminate_on", action="append", default=[], metavar="NAME",
+                   help="asset.terminate_after_contacts_on = the NAMEs given (repeatable, replaces the list): base | hip | thigh | calf | foot; `none` alone empties it, so that only time-outs end an episode")
+    p.add_argument("--penalize_on", action="append", default=[], metavar="NAME",
+                   help="asset.penalize_contacts_on = the NAMEs given (repeatable, replaces the list): base | hip | thigh | calf | foot; `none` alone empties it")
     p.add_argument("--log_root", type=str, default="default")
     args, _ = p.parse_known_args(argv)
     dev = "cuda:{}".format(args.device_id) if args.device == "gpu" else args.device

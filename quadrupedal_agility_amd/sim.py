@@ -45,6 +45,9 @@ class QaSim:
             self.t[name] = self.arena[off:off + n * _ITEM[dt]].view(_TORCH_DT[dt]).view(*shape)
         self._gae_scratch = torch.zeros(4096, dtype=torch.uint8, device=self.device)
         self.global_step = 0
+        # include/qa_sim_reset.h: what the handle does until the setters below are called
+        self.recovery_init_prob = 0.0
+        self.contact_sets = (_capi.DEFAULT_TERMINATION_MASK, _capi.DEFAULT_PENALISED_MASK)
 
     def reset_all(self):
         self.api.launch("reset_all", self.h, self.global_step, on=self.device)
@@ -121,6 +124,19 @@ class QaSim:
         self.self_collision_thighs = bool(on)
         if on:
             self.self_collision_hips = True
+
+    def set_recovery_init(self, prob):
+        """qa_set_recovery_init (include/qa_sim_reset.h): on a step whose one Philox draw falls below `prob`, every env that resets is thrown
+        in tumbled (random roll / pitch / yaw, joints at default x U(0.5, 2), random velocities) instead of taking the handle's reset path.
+        0 switches it off.  The value travels in the launch arguments, so call this before a rollout is recorded."""
+        self.api.call("set_recovery_init", self.h, float(prob))
+        self.recovery_init_prob = float(prob)
+
+    def set_contact_sets(self, termination, penalised):
+        """qa_set_contact_sets (include/qa_sim_reset.h): the body classes (masks of _capi.BODY_CLASS_BITS) whose contact ends the episode /
+        counts for the collision penalty.  The kernels' defaults are base | hip and thigh | calf.  Call it before a rollout is recorded."""
+        self.api.call("set_contact_sets", self.h, int(termination), int(penalised))
+        self.contact_sets = (int(termination), int(penalised))
 
     def step_dev(self, actions, delay, step_counter):
         """qa_env_step_dev: the step counter lives in device memory (graph-replayable)."""
