@@ -390,8 +390,11 @@ QA_DEV void contact_rows(Row *rows, V3 p, int depth, float gap, const V3 *o, con
 // development aid: -DQA_SUBPROF adds s_memtime stamps of the substep's sections (tools/substep_profile.py builds its own
 // copy of the library with it; the product build has none of this)
 #ifdef QA_SUBPROF
-__device__ long long *g_subprof = nullptr;
-#define QA_SUBSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (g_subprof && threadIdx.x == 0) g_subprof[blockIdx.x * 32 + 16 + (k)] = (long long)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#ifndef QA_SUBPROF_PTR
+#define QA_SUBPROF_PTR g_subprof         // qa_sim.hip gives each of its translation units a name of its own
+#endif
+__device__ long long *QA_SUBPROF_PTR = nullptr;
+#define QA_SUBSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (QA_SUBPROF_PTR && threadIdx.x == 0) QA_SUBPROF_PTR[blockIdx.x * 32 + 16 + (k)] = (long long)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define QA_SUBSTAMP(k) do { } while (0)
 #endif

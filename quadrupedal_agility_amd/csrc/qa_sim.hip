@@ -21,6 +21,27 @@
 #include "../../include/qa_sim_rewards.h"
 #include "../../include/qa_sim_selfcol.h"
 #include "../../include/qa_sim_reset.h"
+// This file is compiled once per self-collision level, and QA_SCH_LEVEL says which translation unit this is.  On its own (level 0) it is the
+// library's env engine: every kernel as it always was, the host side and the C ABI.  qa_sim_selfcol.hip (level 1, qa_set_self_collision_hips) and
+// qa_sim_selfcol_thighs.hip (level 2, qa_set_self_collision_thighs on top) set the level and include this file; there it contributes the kernel
+// templates and the level's launchers (qa_env_launchers, below the kernels), which instantiate the kernels that run physics with SCH = QA_SCH_LEVEL.
+// Instantiating those HERE, next to the others, changed the code the compiler generated for the existing kernels (same instructions, another
+// schedule and register assignment), and those are to stay exactly as they are.  What only level 0 has stands in `#if QA_SCH_LEVEL == 0`.
+#ifndef QA_SCH_LEVEL
+#define QA_SCH_LEVEL 0
+#endif
+// A level's cross-unit symbols: the plain name at level 0, name_sch<level> above it.  A code object has its own constant memory, so every level
+// keeps its own copy of the table.  The device symbols keep external linkage: as `static __constant__` the table is reached through a GOT load
+// under -fPIC (an s_load_dwordx2 of the address instead of a pc-relative one), which changes the code of all of the unit's kernels.
+#define QA_LVL_N_(name, n) name##_sch##n
+#define QA_LVL_N(name, n) QA_LVL_N_(name, n)
+#if QA_SCH_LEVEL == 0
+#define QA_LVL(name) name
+#else
+#define QA_LVL(name) QA_LVL_N(name, QA_SCH_LEVEL)
+#endif
+#define QA_SUBPROF_PTR QA_LVL(g_subprof)     // qa_physics.h, -DQA_SUBPROF builds only
+
 #include "qa_go2_model.h"
 #include "qa_physics.h"
 #include "qa_rewards.h"
@@ -30,22 +51,7 @@
 
 static_assert(QA_NUM_LEG_PTS == QA_LEG_PTS && QA_NUM_BASE_PTS == QA_BASE_PTS, "model/table mismatch");
 
-// This file is compiled twice.  On its own it is the library's env engine with the kernels as they always were.  Included by qa_sim_selfcol.hip
-// with QA_SIM_SCH_TU defined it contributes only the kernel templates, which that file instantiates with SCH = 1 (qa_set_self_collision_hips) behind
-// the qa_sch_* launchers declared below: instantiating them HERE, next to the others, changed the code the compiler generated for the existing
-// kernels (same instructions, another schedule and register assignment), and those are to stay exactly as they are.  A code object has its own
-// constant memory, so the second translation unit keeps its own copy of the table (qa_sch_upload_table).  qa_sim_selfcol_thighs.hip is a third
-// one of the same kind: SCH = 2 (qa_set_self_collision_thighs) behind the qa_sct_* launchers, QA_SCH_LEVEL = 2.
-#ifdef QA_SIM_SCH_TU
-#if defined(QA_SCH_LEVEL) && QA_SCH_LEVEL == 2
-#define c_tbl c_tbl_sct
-#define g_subprof g_subprof_sct
-#else
-#define c_tbl c_tbl_sch
-#define g_subprof g_subprof_sch
-#endif
-#endif
-__constant__ float c_tbl[QA_TBL_FLOATS];
+__constant__ float QA_LVL(c_tbl)[QA_TBL_FLOATS];
 
 // ------------------------------------------------------------------ arena layout (ABI: enum order, 256 B aligned)
 struct Layout {
@@ -134,7 +140,7 @@ struct qa_sim {
     long long *prof = nullptr;
     int lanes = 4;                 // lanes per env of the step / simulate kernels (one quad: lane & 3 = leg)
     int lean = 0;                  // qa_set_lean_exports
-    int sc_hips = 0;               // SCH level of the step / simulate kernels: 1 qa_set_self_collision_hips, 2 qa_set_self_collision_thighs on top of it
+    int sc_level = 0;              // SCH level of the step / simulate kernels (index into k_levels): 1 qa_set_self_collision_hips, 2 qa_set_self_collision_thighs on top of it
     int num_cus = 256;             // compute units of the device the arena lives on (launch_env_step: helper wavefronts by launch size)
     qa_config cfg;
     Layout L;
@@ -146,10 +152,10 @@ struct qa_sim {
 
 struct MocapIdx { int32_t on; };      // clips uploaded; the per-gait clip ranges live in column 5 of QA_T_MOCAP_CLIPS
 
-#ifdef QA_SIM_SCH_TU
-extern thread_local char qa_err_buf[512];
-#else
+#if QA_SCH_LEVEL == 0
 thread_local char qa_err_buf[512] = "";      // shared with qa_learner.hip
+#else
+extern thread_local char qa_err_buf[512];
 #endif
 #define g_err qa_err_buf
 static int fail_hip(hipError_t e, const char *what) {
@@ -173,7 +179,7 @@ constexpr int QA_TBL_PER = (QA_TBL_FLOATS + QA_BLOCK - 1) / QA_BLOCK;
 // the table's way into LDS in two halves, so that a kernel can put its other loads between them (one round trip instead of two)
 __device__ __forceinline__ void stage_table_load(float (&v)[QA_TBL_PER]) {
 #pragma unroll
-    for (int r = 0; r < QA_TBL_PER; ++r) { int i = (threadIdx.x & (QA_BLOCK - 1)) + QA_BLOCK * r; v[r] = (i < QA_TBL_FLOATS) ? c_tbl[i] : 0.f; }   // loads in flight together
+    for (int r = 0; r < QA_TBL_PER; ++r) { int i = (threadIdx.x & (QA_BLOCK - 1)) + QA_BLOCK * r; v[r] = (i < QA_TBL_FLOATS) ? QA_LVL(c_tbl)[i] : 0.f; }   // loads in flight together
 }
 __device__ __forceinline__ void stage_table_store(float *s_tbl, const float (&v)[QA_TBL_PER]) {
 #pragma unroll
@@ -1362,7 +1368,7 @@ __device__ __forceinline__ float normal_from(float u1, float u2) {
     return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
 
-#ifndef QA_SIM_SCH_TU
+#if QA_SCH_LEVEL == 0
 struct BaseConst { float m, com[3], I[6]; };
 
 __global__ void qa_init_kernel(qa_config c, Ptrs p, BaseConst bc) {
@@ -1437,7 +1443,7 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_reset_all_kernel(qa_config c, Ptr
     for (int i = leg; i < 570; i += 4) p.obs[(int64_t)env * QA_NUM_OBS + 90 + i] = 0.f;
 }
 
-#endif   // QA_SIM_SCH_TU
+#endif   // QA_SCH_LEVEL == 0
 
 template <bool PLANE, int LPE, int SCH = 0>
 __global__ void __launch_bounds__(QA_BLOCK) qa_simulate_kernel(qa_config c, Ptrs p, const float *torques, const uint8_t *cond) {
@@ -1516,18 +1522,65 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_simulate_kernel(qa_config c, Ptrs
     }
 }
 
-// the launchers of the SCH instantiations (defined in the translation unit of qa_sim_selfcol.hip, see the top of this file)
-int qa_sch_upload_table(const float *tbl, size_t bytes);
-void qa_sch_launch_env_step(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a);
-void qa_sch_launch_physics_step(bool hf, int blocks, hipStream_t st, const StepArgs &a);
-void qa_sch_launch_simulate(bool hf, int blocks, hipStream_t st, const qa_config &c, const Ptrs &p, const float *torques, const uint8_t *cond);
-// and of the SCH = 2 instantiations (qa_sim_selfcol_thighs.hip)
-int qa_sct_upload_table(const float *tbl, size_t bytes);
-void qa_sct_launch_env_step(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a);
-void qa_sct_launch_physics_step(bool hf, int blocks, hipStream_t st, const StepArgs &a);
-void qa_sct_launch_simulate(bool hf, int blocks, hipStream_t st, const qa_config &c, const Ptrs &p, const float *torques, const uint8_t *cond);
+// ------------------------------------------------------------------ this level's launchers
+// Every translation unit (see the top of this file) defines the same four host functions over its SCH = QA_SCH_LEVEL instantiations and exports
+// them as ONE object, QA_LVL(qa_env_level); the level-0 host side reaches the kernels that run physics through k_levels[] only.  A new launch
+// axis is added here, once; a new level is a two-line .hip file and one more entry of k_levels.
+struct qa_env_launchers {
+    int (*upload_table)(const float *tbl);
+    void (*env_step)(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a);
+    void (*physics_step)(bool hf, int blocks, hipStream_t st, const StepArgs &a);
+    void (*simulate)(bool hf, int blocks, hipStream_t st, const qa_config &c, const Ptrs &p, const float *torques, const uint8_t *cond);
+};
 
-#ifndef QA_SIM_SCH_TU
+static int lvl_upload_table(const float *tbl) {
+    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(QA_LVL(c_tbl)), tbl, sizeof(float) * QA_TBL_FLOATS);
+    return e == hipSuccess ? QA_OK : fail_hip(e, QA_SCH_LEVEL == 0 ? "hipMemcpyToSymbol(c_tbl)" : "hipMemcpyToSymbol(c_tbl, self-collision kernels)");
+}
+
+// helpers: two helper wavefronts per workgroup, plane kernels only; xr: qa_set_extra_rewards, the XR instantiations
+static void lvl_env_step(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a) {
+#define QA_LAUNCH_STEP(PLANE_, LEAN_, HELP_) do { \
+        if (xr) hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 1, QA_SCH_LEVEL>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); \
+        else hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 0, QA_SCH_LEVEL>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); } while (0)
+    if (!hf && helpers) {
+        if (lean == 3) QA_LAUNCH_STEP(true, 3, 1);
+        else if (lean == 1) QA_LAUNCH_STEP(true, 1, 1);
+        else QA_LAUNCH_STEP(true, 0, 1);
+        return;
+    }
+    if (lean == 3) {
+        if (hf) QA_LAUNCH_STEP(false, 3, 0);
+        else QA_LAUNCH_STEP(true, 3, 0);
+    } else if (lean == 1) {
+        if (hf) QA_LAUNCH_STEP(false, 1, 0);
+        else QA_LAUNCH_STEP(true, 1, 0);
+    } else {
+        if (hf) QA_LAUNCH_STEP(false, 0, 0);
+        else QA_LAUNCH_STEP(true, 0, 0);
+    }
+#undef QA_LAUNCH_STEP
+}
+
+static void lvl_physics_step(bool hf, int blocks, hipStream_t st, const StepArgs &a) {
+    if (hf) hipLaunchKernelGGL((qa_env_step_kernel<false, 4, 1, 0, 0, 0, QA_SCH_LEVEL>), dim3(blocks), dim3(QA_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 1, 0, 0, 0, QA_SCH_LEVEL>), dim3(blocks), dim3(QA_BLOCK), 0, st, a);
+}
+
+static void lvl_simulate(bool hf, int blocks, hipStream_t st, const qa_config &c, const Ptrs &p, const float *torques, const uint8_t *cond) {
+    if (hf) hipLaunchKernelGGL((qa_simulate_kernel<false, 4, QA_SCH_LEVEL>), dim3(blocks), dim3(QA_BLOCK), 0, st, c, p, torques, cond);
+    else hipLaunchKernelGGL((qa_simulate_kernel<true, 4, QA_SCH_LEVEL>), dim3(blocks), dim3(QA_BLOCK), 0, st, c, p, torques, cond);
+}
+
+extern const qa_env_launchers QA_LVL(qa_env_level);
+#ifndef __HIP_DEVICE_COMPILE__       // host data: the device pass would emit a constant with external linkage into the code object too
+const qa_env_launchers QA_LVL(qa_env_level) = {lvl_upload_table, lvl_env_step, lvl_physics_step, lvl_simulate};
+#endif
+
+#if QA_SCH_LEVEL == 0
+extern const qa_env_launchers QA_LVL_N(qa_env_level, 1), QA_LVL_N(qa_env_level, 2);      // qa_sim_selfcol.hip, qa_sim_selfcol_thighs.hip
+static const qa_env_launchers *const k_levels[3] = {&qa_env_level, &QA_LVL_N(qa_env_level, 1), &QA_LVL_N(qa_env_level, 2)};    // by qa_sim::sc_level
+
 // ------------------------------------------------------------------ fused GAE (rollout_storage.py:97-111)
 // pass 1: one lane per env, reverse scan over T (coalesced across envs); per-block partial sums in double.
 #define GAE_BLOCK 256
@@ -1661,10 +1714,8 @@ int qa_create(const qa_config *cfg, void *arena, int64_t arena_bytes, void *stre
     hipStream_t st = (hipStream_t)stream;
     float tbl[QA_TBL_FLOATS]; build_table(tbl);
     { int dev = 0, cus = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) s->num_cus = cus; }
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_tbl), tbl, sizeof(tbl));
-    if (e != hipSuccess) { delete s; return fail_hip(e, "hipMemcpyToSymbol(c_tbl)"); }
-    if (qa_sch_upload_table(tbl, sizeof(tbl)) != QA_OK || qa_sct_upload_table(tbl, sizeof(tbl)) != QA_OK) { delete s; return QA_E_DEVICE; }
-    e = hipMemsetAsync(arena, 0, (size_t)s->L.total, st);
+    for (const qa_env_launchers *lv : k_levels) if (int rc = lv->upload_table(tbl)) { delete s; return rc; }     // a code object has its own constant memory
+    hipError_t e = hipMemsetAsync(arena, 0, (size_t)s->L.total, st);
     if (e != hipSuccess) { delete s; return fail_hip(e, "hipMemsetAsync(arena)"); }
     if (cfg->terrain_type == 1 && cfg->hf_ceiling) {     // "no overhang anywhere" until the caller writes the ceiling field
         e = hipMemsetD16Async((hipDeviceptr_t)s->p.ceil_samples, (unsigned short)QA_NO_CEILING, (size_t)cfg->hf_rows * cfg->hf_cols, st);
@@ -1700,6 +1751,11 @@ int qa_set_mocap(qa_sim *s, const float *frames, int32_t nf, const double *clips
 
 static MocapIdx mocap_idx(const qa_sim *s) { MocapIdx m; m.on = s->mocap_first[QA_NUM_GAITS] > 0; return m; }
 
+static StepArgs make_step_args(const qa_sim *s, const float *actions, int delay, int64_t step, int64_t *step_ptr, long long *prof) {
+    StepArgs a; a.c = s->cfg; a.p = s->p; a.mi = mocap_idx(s); a.actions = actions; a.delay = delay; a.step = step; a.step_ptr = step_ptr; a.prof = prof;
+    return a;
+}
+
 static void launch_env_step(qa_sim *s, const StepArgs &a, hipStream_t st) {
     const int epb = QA_BLOCK / s->lanes, blocks = (s->cfg.num_envs + epb - 1) / epb;
     const bool hf = s->cfg.terrain_type == 1;
@@ -1708,30 +1764,7 @@ static void launch_env_step(qa_sim *s, const StepArgs &a, hipStream_t st) {
     // 0 = never (the one-wavefront kernels, A/B runs), 1 = always, unset = by launch size
     static const int helpers_switch = [] { const char *e = getenv("QA_ENV_HELPERS"); return e ? (atoi(e) != 0 ? 1 : 0) : QA_ENV_HELPERS_DEFAULT; }();
     const bool helpers = helpers_switch == 1 || (helpers_switch < 0 && blocks <= s->num_cus);
-    const bool xr = s->p.xr_sums != nullptr;           // qa_set_extra_rewards: the XR instantiations
-    // qa_set_self_collision_hips: the SCH instantiations, which live in qa_sim_selfcol.hip
-    if (s->sc_hips == 2) { qa_sct_launch_env_step(hf, s->lean, !hf && helpers, xr, blocks, st, a); return; }      // ... and qa_sim_selfcol_thighs.hip
-    if (s->sc_hips) { qa_sch_launch_env_step(hf, s->lean, !hf && helpers, xr, blocks, st, a); return; }
-#define QA_LAUNCH_STEP(PLANE_, LEAN_, HELP_) do { \
-        if (xr) hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 1>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); \
-        else hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 0>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); } while (0)
-    if (!hf && helpers) {
-        if (s->lean == 3) QA_LAUNCH_STEP(true, 3, 1);
-        else if (s->lean == 1) QA_LAUNCH_STEP(true, 1, 1);
-        else QA_LAUNCH_STEP(true, 0, 1);
-        return;
-    }
-    if (s->lean == 3) {
-        if (hf) QA_LAUNCH_STEP(false, 3, 0);
-        else QA_LAUNCH_STEP(true, 3, 0);
-    } else if (s->lean == 1) {
-        if (hf) QA_LAUNCH_STEP(false, 1, 0);
-        else QA_LAUNCH_STEP(true, 1, 0);
-    } else {
-        if (hf) QA_LAUNCH_STEP(false, 0, 0);
-        else QA_LAUNCH_STEP(true, 0, 0);
-    }
-#undef QA_LAUNCH_STEP
+    k_levels[s->sc_level]->env_step(hf, s->lean, helpers, s->p.xr_sums != nullptr, blocks, st, a);
 }
 
 int qa_set_lean_exports(qa_sim *s, int32_t mask) {
@@ -1757,24 +1790,26 @@ int qa_set_terrain_curriculum(qa_sim *s, int64_t *terrain_levels, const int64_t 
     return QA_OK;
 }
 
-int qa_set_self_collision_hips(qa_sim *s, int on) {
+// the guard of the self-collision setters: the rows of every level belong to the self-collision model
+static int sc_level_settable(const qa_sim *s, int on, const char *fn, const char *rows) {
     if (!s) return QA_E_ARG;
     if (on && !s->cfg.self_collision) {
-        snprintf(g_err, sizeof(g_err), "qa_set_self_collision_hips: the handle was created with self_collision = 0 (the calf-hip rows belong to the self-collision model)");
+        snprintf(g_err, sizeof(g_err), "%s: the handle was created with self_collision = 0 (the %s rows belong to the self-collision model)", fn, rows);
         return QA_E_ARG;
     }
-    s->sc_hips = on ? 1 : 0;
+    return QA_OK;
+}
+
+int qa_set_self_collision_hips(qa_sim *s, int on) {
+    if (int rc = sc_level_settable(s, on, "qa_set_self_collision_hips", "calf-hip")) return rc;
+    s->sc_level = on ? 1 : 0;
     return QA_OK;
 }
 
 int qa_set_self_collision_thighs(qa_sim *s, int on) {
-    if (!s) return QA_E_ARG;
-    if (on && !s->cfg.self_collision) {
-        snprintf(g_err, sizeof(g_err), "qa_set_self_collision_thighs: the handle was created with self_collision = 0 (the calf-thigh rows belong to the self-collision model)");
-        return QA_E_ARG;
-    }
-    if (on) s->sc_hips = 2;
-    else if (s->sc_hips == 2) s->sc_hips = 1;
+    if (int rc = sc_level_settable(s, on, "qa_set_self_collision_thighs", "calf-thigh")) return rc;
+    if (on) s->sc_level = 2;
+    else if (s->sc_level == 2) s->sc_level = 1;
     return QA_OK;
 }
 
@@ -1818,8 +1853,7 @@ int qa_set_contact_sets(qa_sim *s, uint32_t termination_mask, uint32_t penalised
 int qa_env_step(qa_sim *s, const float *actions, int32_t delay_steps, int64_t global_step, void *stream) {
     if (!s || !actions || delay_steps < 0 || delay_steps >= QA_ACTION_BUF_LEN) return QA_E_ARG;
     if (s->lean && delay_steps > 1) { snprintf(g_err, sizeof(g_err), "qa_env_step: lean exports keep two action slots (delay <= 1)"); return QA_E_ARG; }
-    StepArgs a; a.c = s->cfg; a.p = s->p; a.mi = mocap_idx(s); a.actions = actions; a.delay = delay_steps; a.step = global_step; a.step_ptr = nullptr; a.prof = s->prof;
-    launch_env_step(s, a, (hipStream_t)stream);
+    launch_env_step(s, make_step_args(s, actions, delay_steps, global_step, nullptr, s->prof), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return QA_OK;
 }
@@ -1827,21 +1861,15 @@ int qa_env_step(qa_sim *s, const float *actions, int32_t delay_steps, int64_t gl
 int qa_env_step_dev(qa_sim *s, const float *actions, int32_t delay_steps, int64_t *step_counter_dev, void *stream) {
     if (!s || !actions || !step_counter_dev || delay_steps < 0 || delay_steps >= QA_ACTION_BUF_LEN) return QA_E_ARG;
     if (s->lean && delay_steps > 1) { snprintf(g_err, sizeof(g_err), "qa_env_step_dev: lean exports keep two action slots (delay <= 1)"); return QA_E_ARG; }
-    StepArgs a; a.c = s->cfg; a.p = s->p; a.mi = mocap_idx(s); a.actions = actions; a.delay = delay_steps; a.step = 0;
-    a.step_ptr = step_counter_dev; a.prof = s->prof;
-    launch_env_step(s, a, (hipStream_t)stream);
+    launch_env_step(s, make_step_args(s, actions, delay_steps, 0, step_counter_dev, s->prof), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return QA_OK;
 }
 
 int qa_env_physics_step(qa_sim *s, const float *actions, int32_t delay_steps, void *stream) {
     if (!s || !actions || delay_steps < 0 || delay_steps >= QA_ACTION_BUF_LEN) return QA_E_ARG;
-    StepArgs a; a.c = s->cfg; a.p = s->p; a.mi = mocap_idx(s); a.actions = actions; a.delay = delay_steps; a.step = 0; a.step_ptr = nullptr; a.prof = nullptr;
     const int blocks = (s->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
-    if (s->sc_hips == 2) qa_sct_launch_physics_step(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, a);  // the SCH = 2 instantiations (qa_sim_selfcol_thighs.hip)
-    else if (s->sc_hips) qa_sch_launch_physics_step(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, a);  // the SCH instantiations (qa_sim_selfcol.hip)
-    else if (s->cfg.terrain_type == 1) hipLaunchKernelGGL((qa_env_step_kernel<false, 4, 1>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 1>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, a);
+    k_levels[s->sc_level]->physics_step(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, make_step_args(s, actions, delay_steps, 0, nullptr, nullptr));
     HIP_TRY(hipGetLastError());
     return QA_OK;
 }
@@ -1858,10 +1886,7 @@ static int launch_simulate(qa_sim *s, const float *torques, const uint8_t *cond,
     if (!s) return QA_E_ARG;
     if (!torques) torques = s->p.torques;          // the actuation forces set last (gym keeps applying them)
     const int epb = QA_BLOCK / s->lanes, blocks = (s->cfg.num_envs + epb - 1) / epb;
-    if (s->sc_hips == 2) qa_sct_launch_simulate(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, s->cfg, s->p, torques, cond);  // the SCH = 2 instantiations (qa_sim_selfcol_thighs.hip)
-    else if (s->sc_hips) qa_sch_launch_simulate(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, s->cfg, s->p, torques, cond);  // the SCH instantiations (qa_sim_selfcol.hip)
-    else if (s->cfg.terrain_type == 1) hipLaunchKernelGGL((qa_simulate_kernel<false, 4>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, s->cfg, s->p, torques, cond);
-    else hipLaunchKernelGGL((qa_simulate_kernel<true, 4>), dim3(blocks), dim3(QA_BLOCK), 0, (hipStream_t)stream, s->cfg, s->p, torques, cond);
+    k_levels[s->sc_level]->simulate(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, s->cfg, s->p, torques, cond);
     HIP_TRY(hipGetLastError());
     return QA_OK;
 }
@@ -1933,7 +1958,7 @@ int qa_tsc_reset_dev(qa_sim *s, const uint8_t *reset_flags, const float *start_x
 
 int qa_debug_post_physics(qa_sim *s, int64_t global_step, void *stream) {
     if (!s) return QA_E_ARG;
-    StepArgs a; a.c = s->cfg; a.p = s->p; a.mi = mocap_idx(s); a.actions = nullptr; a.delay = 0; a.step = global_step; a.step_ptr = nullptr; a.prof = nullptr;
+    const StepArgs a = make_step_args(s, nullptr, 0, global_step, nullptr, nullptr);
     const int blocks = (s->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
     const bool hf = s->cfg.terrain_type == 1;
     if (s->p.xr_sums) {       // qa_set_extra_rewards: the XR instantiations
@@ -1950,7 +1975,7 @@ int qa_debug_set_profile_buffer(qa_sim *s, long long *dev_buf) {
     if (!s) return QA_E_ARG;
     s->prof = dev_buf;
 #ifdef QA_SUBPROF
-    hipMemcpyToSymbol(HIP_SYMBOL(g_subprof), &dev_buf, sizeof(dev_buf));
+    hipMemcpyToSymbol(HIP_SYMBOL(g_subprof), &dev_buf, sizeof(dev_buf));      // level 0's pointer only: the substep profile measures the kernels without the extra rows
 #endif
     return QA_OK;
 }
@@ -1972,4 +1997,4 @@ int qa_gae(const float *rewards, const float *values, const uint8_t *dones, cons
 }
 
 }  // extern "C"
-#endif   // QA_SIM_SCH_TU
+#endif   // QA_SCH_LEVEL == 0
