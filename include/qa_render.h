@@ -1,0 +1,82 @@
+/* qa_render.h -- extension of include/qa_sim.h: frames of the robot over its ground, for looking at a policy (play.py --record_frames).
+ *
+ * A sibling of qa_tsc_depth_obstacles.h and kept apart from qa_sim.h for the same reason: no arena tensor, no config field, no oracle twin
+ * (the float64 restatement in tests/render_ref.py is the twin).  The library exports the entry points next to the ABI; the Python side binds
+ * them through _capi.EXTENSION_SYMBOLS.  Stateless like qa_tsc_depth_update: a cfg and an io struct, no qa_sim handle, and READ-ONLY on
+ * everything but the three output images.
+ *
+ * One launch renders K cameras.  Camera k looks at env env_ids[k] and sees that env's robot only -- the 19 bodies as the primitives of
+ * quadrupedal_agility_amd/csrc/qa_render_shapes.h, posed by the env's QA_T_RIGID_BODY_STATE rows -- over the ground:
+ *   terrain_type 0   the plane z = 0
+ *   terrain_type 1   the height field's two-triangle cell surface with the clamped lookup of collision and of the depth camera (outside the
+ *                    map the border's edge continues), plus the ceiling map where given; a ceiling triangle with a QA_NO_CEILING corner
+ *                    does not exist.  The articulated obstacles are drawn as built (the static maps), not in their joint state.
+ * Pinhole camera: eye, target, vertical field of view; up = +z (a camera looking straight up or down takes +x as up).  Pixel (i, j) looks
+ * through ((j + 0.5) / width, (i + 0.5) / height) of the image plane, row 0 at the top.
+ * Shading: a fixed colour per class (trunk, hip, thigh, calf, foot, ground, ceiling, sky) x (ambient + (1 - ambient) max(0, n.l)); the
+ * ground carries a checker of 0.5 m in world x / y; with QA_RENDER_SHADOWS a ground point whose ray towards the light meets the robot
+ * keeps the ambient term alone.
+ */
+#ifndef QA_RENDER_H
+#define QA_RENDER_H
+
+#include "qa_sim.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define QA_RENDER_SHADOWS 1         /* flags: one shadow ray per ground hit, against the robot's primitives */
+#define QA_RENDER_CHECKER 2         /* flags: the 0.5 m checker on the ground */
+
+#define QA_RENDER_ID_GROUND 19      /* ids: 0..18 = the body (QA_T_RIGID_BODY_STATE row), then */
+#define QA_RENDER_ID_CEILING 20
+#define QA_RENDER_ID_SKY (-1)
+
+#define QA_RENDER_AMBIENT 0.35f
+#define QA_RENDER_CHECKER_SIZE 0.5f
+#define QA_RENDER_CHECKER_DARK 0.8f /* the odd squares' colour factor */
+
+typedef struct qa_render_cfg {
+    int32_t num_envs;               /* N: rows of body_state */
+    int32_t num_cameras;            /* K */
+    int32_t width, height;
+    int32_t terrain_type;           /* 0 plane, 1 height field */
+    int32_t map_rows, map_cols;     /* terrain_type 1 */
+    float border_size, horizontal_scale, vertical_scale;
+    float far;                      /* rays end here: a hit is nearer than `far` */
+    float light_dir[3];             /* TOWARDS the light, world frame, any length > 0 */
+    int32_t flags;                  /* QA_RENDER_* */
+} qa_render_cfg;
+
+typedef struct qa_render_io {
+    const float *body_state;        /* (N,19,13) device: QA_T_RIGID_BODY_STATE (qa_config.export_body_state = 1), read when the launch executes */
+    const int32_t *env_ids;         /* (K) device.  The kernel clamps an entry to [0, N) */
+    const int32_t *env_ids_host;    /* (K) host copy of env_ids or NULL: when given, an entry outside [0, N) is refused before the launch */
+    const float *cameras;           /* (K,7) device: eye xyz, target xyz, vertical fov in radians */
+    const int16_t *height_samples;  /* (map_rows, map_cols) device; terrain_type 1 */
+    const int16_t *ceiling_samples; /* same grid or NULL */
+    uint8_t *rgb;                   /* (K,H,W,3) device */
+    float *depth;                   /* (K,H,W) device or NULL: distance along the ray, `far` on a miss */
+    int8_t *ids;                    /* (K,H,W) device or NULL: QA_RENDER_ID_* */
+} qa_render_io;
+
+/* One launch on `stream`, grid (tiles of 16 x 16 pixels, K).  Nothing is allocated or read back: the call can be recorded into a hipGraph.
+ * QA_E_ARG (with qa_last_error() text) and NO launch for: a NULL cfg / io / rgb / body_state / env_ids / cameras; num_cameras < 1;
+ * num_envs < 1; width or height < 1 or K * width * height * 3 past int32; an env_ids_host entry outside [0, N); terrain_type other than
+ * 0 / 1; terrain_type 1 without height_samples, with map_rows or map_cols < 2 or horizontal_scale <= 0; far <= 0, or on a height field
+ * far > 1e6 horizontal_scale; a zero light_dir; num_cameras > 65535. */
+int qa_render_frames(const qa_render_cfg *cfg, const qa_render_io *io, void *stream);
+
+/* the primitive table of qa_render_shapes.h as the library was built with it: writes min(cap, count) records of 10 floats
+ * (kind, body, class, a[3], b[3], r) and returns the count.  Host only, touches no device. */
+int qa_render_shape_table(float *out, int cap);
+/* the palette: QA_RS_NUM_CLASSES x 3 floats in [0, 1] */
+int qa_render_palette(float *out);
+/* sizeof the two structs, for the binding's layout check */
+int qa_render_sizeof(int which);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -262,6 +262,11 @@ def bind_extensions(lib, prefix="qa_"):
     f = getattr(lib, prefix + "tsc_goal_step_rewards"); f.argtypes = [C.POINTER(QaTscGoalCfg), C.POINTER(QaTscGoalIo), C.POINTER(QaTscExtraRewards), C.c_void_p]; f.restype = C.c_int
     # include/qa_tsc_depth_obstacles.h
     f = getattr(lib, prefix + "tsc_depth_update_obstacles"); f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(QaTscDepthObstacles), C.c_void_p]; f.restype = C.c_int
+    # include/qa_render.h
+    f = getattr(lib, prefix + "render_frames"); f.argtypes = [C.POINTER(QaRenderCfg), C.POINTER(QaRenderIo), C.c_void_p]; f.restype = C.c_int
+    f = getattr(lib, prefix + "render_shape_table"); f.argtypes = [C.c_void_p, C.c_int]; f.restype = C.c_int
+    f = getattr(lib, prefix + "render_palette"); f.argtypes = [C.c_void_p]; f.restype = C.c_int
+    f = getattr(lib, prefix + "render_sizeof"); f.argtypes = [C.c_int]; f.restype = C.c_int
     return lib
 
 
@@ -275,6 +280,27 @@ class QaExtraRewards(C.Structure):
 class QaTscDepthObstacles(C.Structure):
     """qa_tsc_depth_obstacles of include/qa_tsc_depth_obstacles.h"""
     _fields_ = [("obst_desc", C.c_void_p), ("obst_state", C.c_void_p)]
+
+
+RENDER_SHADOWS, RENDER_CHECKER = 1, 2                 # QA_RENDER_* flags of include/qa_render.h
+RENDER_ID_GROUND, RENDER_ID_CEILING, RENDER_ID_SKY = 19, 20, -1
+RENDER_AMBIENT, RENDER_CHECKER_SIZE, RENDER_CHECKER_DARK = 0.35, 0.5, 0.8
+RENDER_SPHERE, RENDER_CAPSULE, RENDER_BOX = 0, 1, 2    # QA_RS_* kinds of csrc/qa_render_shapes.h
+
+
+class QaRenderCfg(C.Structure):
+    """qa_render_cfg of include/qa_render.h"""
+    _fields_ = [("num_envs", C.c_int32), ("num_cameras", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("terrain_type", C.c_int32),
+                ("map_rows", C.c_int32), ("map_cols", C.c_int32), ("border_size", C.c_float), ("horizontal_scale", C.c_float),
+                ("vertical_scale", C.c_float), ("far", C.c_float), ("light_dir", C.c_float * 3), ("flags", C.c_int32)]
+
+
+RENDER_IO_FIELDS = ("body_state", "env_ids", "env_ids_host", "cameras", "height_samples", "ceiling_samples", "rgb", "depth", "ids")
+
+
+class QaRenderIo(C.Structure):
+    """qa_render_io of include/qa_render.h (every member is a pointer)"""
+    _fields_ = [(name, C.c_void_p) for name in RENDER_IO_FIELDS]
 
 
 class QaTscObstCurr(C.Structure):
@@ -427,9 +453,10 @@ ABI_SYMBOLS = ["arena_bytes", "create", "destroy", "tensor_info", "env_step", "e
                "set_mocap", "debug_post_physics", "env_physics_step", "tsc_reset", "tsc_reset_dev", "simulate_if", "gae", "ppo_loss", "ppo_loss_scratch_bytes", "hybrid_ppo_loss", "hybrid_ppo_loss_scratch_bytes", "elu_backward_bias",
                "elu_backward_bias_scratch_bytes", "narrow_wgrad", "narrow_wgrad_scratch_bytes", "linear_forward", "linear_backward_input", "linear_backward_weight", "linear_backward_weight_scratch_bytes", "linear_backward_weight_layout", "linear_backward_weight_batch", "linear_backward_weight_batch_layout", "linear_backward_weight_batch_scratch_bytes", "slab_sum", "linear_forward_split", "linear_forward_split_scratch_bytes", "depth_stem_forward", "depth_stem_backward", "depth_stem_backward_scratch_bytes", "conv_nhwc_forward", "conv_nhwc_backward_input", "conv_nhwc_backward_weight", "conv_nhwc_backward_weight_scratch_bytes", "elu_backward_pad", "normalizer_update", "normalizer_apply", "clip_adam_step", "clip_adam_step_hostgrads", "clip_adam_step_reduce", "clip_adam_pair_step", "grad_reduce", "adam_stack_step", "rollout_act", "rollout_act_store", "rollout_act_hybrid", "rollout_post", "rollout_post_amp", "disc_loss", "disc_loss_logits", "disc_loss_scratch_bytes", "disc_prepare", "disc_sample_prepare", "disc_step_tail", "disc_step_tail_scratch_bytes", "pair_loss", "pair_loss_scratch_bytes", "pair_losses", "pair_losses_scratch_bytes", "accumulate_scalars", "gather_rows", "kl_lr_rule", "episode_means", "set_lean_exports", "mlp_packed_floats", "mlp_pack", "mlp_forward", "mlp_strands", "mlp_groups", "mlp_set_groups", "tsc_set_commands", "tsc_goal_step", "tsc_observations", "tsc_depth_update", "tsc_reset_stats", "tsc_push", "tsc_start_pose", "tsc_reset_where", "last_error", "abi_version"]
 # include/qa_sim_curriculum.h, include/qa_tsc_curriculum.h, include/qa_sim_rewards.h, include/qa_sim_selfcol.h, include/qa_tsc_rewards.h,
-# include/qa_tsc_depth_obstacles.h (bind_extensions)
+# include/qa_tsc_depth_obstacles.h, include/qa_render.h (bind_extensions)
 EXTENSION_SYMBOLS = ["set_terrain_curriculum", "tsc_obstacle_curriculum", "set_extra_rewards", "set_self_collision_hips", "set_self_collision_thighs", "tsc_goal_step_rewards",
-                     "tsc_depth_update_obstacles", "set_recovery_init", "set_contact_sets"]
+                     "tsc_depth_update_obstacles", "set_recovery_init", "set_contact_sets", "render_frames", "render_shape_table", "render_palette",
+                     "render_sizeof"]
 
 _LIB = None
 # QA_LIB: another build of the SAME library (A/B measurements of a kernel variant, tools/r5_call.sh); there is still no fallback -- a missing file raises

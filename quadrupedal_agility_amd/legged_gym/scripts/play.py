@@ -1,8 +1,10 @@
 """python -m quadrupedal_agility_amd.legged_gym.scripts.play --task go2_locomotion [--load_run R] [--checkpoint K]
 Drop-in for bbc/legged_gym/scripts/play.py:14-125: same config overrides, checkpoint resume, inference policy
-(history-encoder latent), fixed gait/velocity command, state/reward logging.  There is no viewer in this build, so
-the camera/frame-recording branches are gone and the loop length is a flag (`--num_steps`; the reference runs
-1000 episodes' worth); `--export_policy` writes the TorchScript deployment module (helpers.export_policy_as_jit)."""
+(history-encoder latent), fixed gait/velocity command, state/reward logging.  There is no viewer in this build and the loop
+length is a flag (`--num_steps`; the reference runs 1000 episodes' worth); `--export_policy` writes the TorchScript deployment module
+(helpers.export_policy_as_jit).  `--record_frames [DIR]` is the reference's RECORD_FRAMES branch (:60,75-84): every `--record_every`-th step
+(default 2) a HIP ray-cast of the robot over its ground is written to DIR/<n>.png (default logs/<experiment_name>/exported/frames), from a
+camera that follows the robot at the reference's camera_pos_bias (quadrupedal_agility_amd/render.py)."""
 import argparse
 import os
 import time
@@ -66,6 +68,14 @@ def play(args, num_steps=None, export_policy=False, realtime=False, gait=2, vel_
     env.latent_c[:, gait] = 1
     env.commands[:, 0] = vel_x
 
+    recorder = None
+    from quadrupedal_agility_amd.render import record_settings
+    rec = record_settings(args, train_cfg.runner.experiment_name)
+    if rec is not None:                      # without --record_frames nothing of the renderer is constructed or launched
+        from quadrupedal_agility_amd.render import FrameRecorder
+        recorder = FrameRecorder(env, **rec)
+    env.frame_recorder = recorder
+
     n = int(num_steps) if num_steps is not None else 1000 * int(env.max_episode_length)
     for i in range(n):
         t0 = time.time()
@@ -74,6 +84,8 @@ def play(args, num_steps=None, export_policy=False, realtime=False, gait=2, vel_
         with torch.no_grad():
             actions = policy(obs.detach())
         obs, _, rews, dones, infos, _, _ = env.step(actions.detach())
+        if recorder is not None:
+            recorder.capture(i)
         if i < stop_state_log:
             logger.log_states({
                 "dof_pos_target": env.default_dof_pos[0, :].cpu().numpy() + env.cfg.control.action_scale * env.actions[robot_index, :].cpu().numpy(),

@@ -33,6 +33,8 @@ def make_qa_config(cfg, seed=1, sim_dt=None, terrain=None):
     qa = getattr(cfg.sim, "qa", None)
     c.solver_iterations = int(getattr(qa, "solver_iterations", 4))
     c.contact_slots = int(getattr(qa, "contact_slots", 2))
+    # RIGID_BODY_STATE (N,19,13) refreshed every step: off unless asked for (play.py --record_frames: render.FrameRecorder draws from it)
+    c.export_body_state = int(getattr(qa, "export_body_state", 0))
     # asset.self_collisions: 0 = ENABLED, 1 = disabled (the reference's bitwise filter flag, go2_locomotion_config.py:72)
     c.self_collision = int(getattr(cfg.asset, "self_collisions", 0) == 0)
     c.contact_offset = float(cfg.sim.physx.contact_offset)

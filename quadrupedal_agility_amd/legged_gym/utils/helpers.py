@@ -100,6 +100,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             env_cfg.asset.qa_self_collision_thighs = True
         if getattr(args, "no_mocap_init", False):
             env_cfg.env.mocap_state_init = False
+        if getattr(args, "record_frames", None) is not None:
+            env_cfg.sim.qa.export_body_state = 1         # the frame recorder draws the robot from RIGID_BODY_STATE
         if getattr(args, "recovery_init_prob", None) is not None:
             env_cfg.env.recovery_init_prob = args.recovery_init_prob
         for flag, field in (("terminate_on", "terminate_after_contacts_on"), ("penalize_on", "penalize_contacts_on")):
@@ -175,6 +177,8 @@ def get_args(argv=None):
     p.add_argument("--penalize_on", action="append", default=[], metavar="NAME",
                    help="asset.penalize_contacts_on = the NAMEs given (repeatable, replaces the list): base | hip | thigh | calf | foot; `none` alone empties it")
     p.add_argument("--log_root", type=str, default="default")
+    from quadrupedal_agility_amd.render import add_record_args
+    add_record_args(p)                  # --record_frames [DIR] --record_envs --record_every --frame_size (play.py)
     args, _ = p.parse_known_args(argv)
     dev = "cuda:{}".format(args.device_id) if args.device == "gpu" else args.device
     args.rl_device = args.rl_device or dev

@@ -1,7 +1,9 @@
 """tsc/legged_gym/scripts/play.py without the viewer: the reference's test-time overrides (:16-41), a resumed runner, and the
 deployment loop -- estimator -> (depth encoder -> student actor | teacher actor) -> set_commands -> frozen behaviour policy ->
 env.step -- for `--num_steps` steps; prints and returns the course success rate (`reach_goal` of the finished episodes).
-`python -m quadrupedal_agility_amd.tsc.legged_gym.scripts.play --task go2 --exptid <run> [--use_camera] [--num_steps N]`"""
+`python -m quadrupedal_agility_amd.tsc.legged_gym.scripts.play --task go2 --exptid <run> [--use_camera] [--num_steps N]`
+`--record_frames [DIR]` (the reference's RECORD_FRAMES, :135): every `--record_every`-th step a HIP ray-cast of the robot over the course's
+floor and ceiling maps is written to DIR/<n>.png (default logs/<experiment_name>/exported/frames); quadrupedal_agility_amd/render.py."""
 import statistics
 from collections import deque
 
@@ -46,6 +48,12 @@ def play(args, num_steps=1000, env_kwargs=None, quiet=False):
     obs, obs_bbc = env.get_observations().clone(), env.get_observations_bbc().clone()
     infos = {"depth": env.depth_buffer[:, -1].clone() if use_depth else None}
     reach_goal_buffer = deque(maxlen=1000)
+    recorder = None
+    from quadrupedal_agility_amd.render import COURSE_OFFSET, record_settings
+    rec = record_settings(args, train_cfg.runner.experiment_name, default_offset=COURSE_OFFSET)
+    if rec is not None:                      # without --record_frames nothing of the renderer is constructed or launched
+        from quadrupedal_agility_amd.render import FrameRecorder
+        recorder = FrameRecorder(env, **rec)
     depth_latent = delta_yaw = obst_type = None
     with torch.no_grad():
         for i in range(num_steps):
@@ -65,6 +73,8 @@ def play(args, num_steps=1000, env_kwargs=None, quiet=False):
             obs_bbc[:, -(6 + env.dim_c):] = env.set_commands(actions)
             o, _, rews, dones, infos, _, _ = env.step(policy_bbc(obs_bbc, hist_encoding=True))
             obs, obs_bbc = o.clone(), env.get_observations_bbc().clone()
+            if recorder is not None:
+                recorder.capture(i)
             done = dones != 0
             if bool(done.any()):
                 reach_goal_buffer.extend(infos["reach_goal"][done].float().cpu().tolist())

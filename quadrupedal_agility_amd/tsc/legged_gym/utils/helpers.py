@@ -129,6 +129,8 @@ def get_args(argv=None):
     p.add_argument("--physics_engine", default="qa")
     p.add_argument("--bbc_path", type=str, default=None, help="behaviour-level model.pt (default: <root>/<runner.bbc_path>)")
     p.add_argument("--log_root", type=str, default="default")
+    from quadrupedal_agility_amd.render import add_record_args
+    add_record_args(p)                  # --record_frames [DIR] --record_envs --record_every --frame_size (play.py)
     args, _ = p.parse_known_args(argv)
     dev = "cuda:{}".format(args.device_id) if args.device == "gpu" else args.device
     args.rl_device = args.rl_device or dev
