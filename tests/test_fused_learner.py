@@ -42,7 +42,6 @@ def reference(t, clipped=True):
 
 def oracle(t, clipped=True):
     lib = load_oracle()
-    lib.qo_ppo_loss.argtypes = [C.c_void_p] * 10 + [C.c_int64, C.c_int32] + [C.c_float] * 5 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]
     a = {k: np.ascontiguousarray(v.detach().cpu().numpy(), dtype=np.float32) for k, v in t.items()}
     B = a["mu"].shape[0]
     dmu = np.zeros((B, 12), np.float32); dstd = np.zeros(12, np.float32); dval = np.zeros(B, np.float32); out = np.zeros(8, np.float32)
@@ -67,7 +66,6 @@ def test_oracle_matches_eager_pytorch(B, clipped):
 
 def test_oracle_rejects_bad_arguments():
     lib = load_oracle()
-    lib.qo_ppo_loss.argtypes = [C.c_void_p] * 10 + [C.c_int64, C.c_int32] + [C.c_float] * 5 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]
     assert lib.qo_ppo_loss(*([None] * 10), 4, 12, 0.2, 1, 1, 1, 1, 1, *([None] * 5), 0, None) == -1
 
 
@@ -138,7 +136,6 @@ def elu_case(rows, cols, seed):
 def test_elu_backward_bias_oracle_matches_pytorch(rows, cols):
     y, gy = elu_case(rows, cols, rows + cols)
     lib = load_oracle()
-    lib.qo_elu_backward_bias.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]
     yn, gn = y.numpy().copy(), gy.numpy().copy()
     gin = np.zeros_like(yn); gb = np.zeros(cols, np.float32)
     assert lib.qo_elu_backward_bias(gn.ctypes.data, yn.ctypes.data, gin.ctypes.data, gb.ctypes.data, rows, cols, 1.0, None, 0, None) == 0
@@ -153,7 +150,6 @@ def test_elu_backward_bias_oracle_with_alpha_zero_is_the_relu_backward(rows, col
     g = torch.Generator().manual_seed(rows)
     y = torch.relu(torch.randn(rows, cols, generator=g)); gy = torch.randn(rows, cols, generator=g)
     lib = load_oracle()
-    lib.qo_elu_backward_bias.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]
     yn, gn = y.numpy().copy(), gy.numpy().copy()
     gin = np.zeros_like(yn); gb = np.zeros(cols, np.float32)
     assert lib.qo_elu_backward_bias(gn.ctypes.data, yn.ctypes.data, gin.ctypes.data, gb.ctypes.data, rows, cols, 0.0, None, 0, None) == 0
@@ -214,8 +210,6 @@ def test_normalizer_oracle_matches_reference_class():
     """oracle C vs the numpy Normalizer the reference pickles into model.pt (mirror of bbc/rsl_rl/utils/utils.py:62-103)"""
     from quadrupedal_agility_amd.rsl_rl.utils.utils import Normalizer
     lib = load_oracle()
-    lib.qo_normalizer_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.qo_normalizer_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     ref = Normalizer(98); ref32 = Normalizer(98)
     mean = ref.mean.astype(np.float64).copy(); var = ref.var.astype(np.float64).copy(); count = np.array([ref.count], np.float64)
     for rnd in range(3):
@@ -352,7 +346,6 @@ def _fake_grads(a, b, k, scale):
 def test_clip_adam_oracle_matches_pytorch():
     a, b, oa, ob = _adam_twins("cpu", wd=1e-3)
     lib = load_oracle()
-    lib.qo_clip_adam_step.argtypes = [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p, C.c_int64, C.c_void_p]
     ps = list(b.parameters())
     m = [np.zeros(p.numel(), np.float32) for p in ps]; v = [np.zeros(p.numel(), np.float32) for p in ps]; st = [np.zeros(1, np.float32) for _ in ps]
     pn = [p.detach().numpy().reshape(-1).copy() for p in ps]
@@ -455,9 +448,7 @@ def test_clip_adam_pair_twin_equals_its_halves():
     """the C twin of the pair entry against the single-optimiser twin called twice with the rule between (host tables)"""
     lib = load_oracle()
     single = lib.qo_clip_adam_step_reduce
-    single.argtypes = [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 4
     pairf = lib.qo_clip_adam_pair_step
-    pairf.argtypes = [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 5
     from quadrupedal_agility_amd._capi import QaAdamPair
     rng = np.random.default_rng(4)
     sizes = [53 * 16, 16, 16 * 3, 101 * 40, 40, 5000]
@@ -517,16 +508,11 @@ def _rollout_case(N, seed):
                 time_out=(torch.rand(N, generator=g) < 0.1).to(torch.uint8), cur=torch.rand(6, N, generator=g))
 
 
-def _bind_rollout(lib, prefix):
-    getattr(lib, prefix + "rollout_act").argtypes = [C.c_void_p] * 4 + [C.c_uint64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 7
-    getattr(lib, prefix + "rollout_post").argtypes = [C.c_void_p] * 4 + [C.c_float, C.c_float, C.c_int32] + [C.c_void_p] * 6
-
-
 def test_rollout_kernels_oracle_matches_pytorch_expressions():
     from torch.distributions import Normal
     N = 777
     c = _rollout_case(N, 1)
-    lib = load_oracle(); _bind_rollout(lib, "qo_")
+    lib = load_oracle()
     n = {k: np.ascontiguousarray(v.numpy()) for k, v in c.items()}
     out = {k: np.zeros((N, 12), np.float32) for k in ("actions", "sa", "smu", "ssig")}
     logp = np.zeros(N, np.float32); sval = np.zeros(N, np.float32)
@@ -560,7 +546,7 @@ def test_rollout_kernels_hip_match_oracle():
     from quadrupedal_agility_amd import _capi
     N = 4099
     c = _rollout_case(N, 2)
-    lo = load_oracle(); _bind_rollout(lo, "qo_")
+    lo = load_oracle()
     lib = _capi.load_library()
     n = {k: np.ascontiguousarray(v.numpy()) for k, v in c.items()}
     d = {k: v.cuda() for k, v in c.items()}
@@ -620,7 +606,6 @@ def test_rollout_act_store_is_rollout_act_plus_the_row_copy(N):
 
 def test_rollout_act_store_twin():
     lo = load_oracle()
-    lo.qo_rollout_act_store.argtypes = [C.c_void_p] * 4 + [C.c_uint64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
     N = 37
     n = {k: np.ascontiguousarray(v.numpy()) for k, v in _rollout_case(N, 4).items()}
     p = lambda x: x.ctypes.data
@@ -675,7 +660,6 @@ def _disc_reference(t, sizes, info_coef, dev="cpu"):
 
 def _disc_oracle(t, sizes, info_coef):
     lib = load_oracle()
-    lib.qo_disc_loss.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]
     n = {k: np.ascontiguousarray(v.numpy()) for k, v in t.items()}
     B = sum(sizes)
     gd = np.zeros(B, np.float32); ge = np.zeros(B, np.float32); gc = np.zeros((B, 5), np.float32); out = np.zeros(16, np.float32)
@@ -740,8 +724,6 @@ def test_disc_loss_from_logits_is_softmax_loss_softmax_backward(sizes):
 
 def test_disc_loss_logits_twin_equals_softmax_around_the_twin():
     lib = load_oracle()
-    sig = [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]
-    lib.qo_disc_loss.argtypes = sig; lib.qo_disc_loss_logits.argtypes = sig
     b_lb, b_pi, b_ulb = 5, 7, 6
     B = 18
     r = np.random.default_rng(1)
@@ -805,7 +787,6 @@ def _prep_eager(bs, task, fm, w, mean, var):
 def test_disc_prepare_oracle_matches_eager():
     bs, task, fm, w, mean, var = _prep_case(3)
     lib = load_oracle()
-    lib.qo_disc_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     n = [np.ascontiguousarray(b.numpy()) for b in bs]
     ptrs = (C.c_void_p * 3)(*[x.ctypes.data for x in n]); rows = (C.c_int64 * 3)(*[x.shape[0] for x in n])
     out = np.zeros((sum(x.shape[0] for x in n), 98), np.float32)
@@ -919,14 +900,11 @@ def test_pair_losses_twin_equals_the_single_twin():
     jobs = (QaPairJob * 2)()
     jobs[0] = QaPairJob(p.ctypes.data, h.ctypes.data, rows, 29, 0, 29, coef.ctypes.data, g1.ctypes.data, o1.ctypes.data)
     jobs[1] = QaPairJob(est.ctypes.data, wide.ctypes.data + 28, rows, 4, 1, 53, None, g2.ctypes.data, o2.ctypes.data)
-    lib.qo_pair_losses_scratch_bytes.restype = C.c_int64; lib.qo_pair_losses_scratch_bytes.argtypes = [C.c_void_p, C.c_int32]
-    lib.qo_pair_losses.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
     nb = lib.qo_pair_losses_scratch_bytes(C.cast(jobs, C.c_void_p), 2)
     assert nb == 4 * (2 * 3 + 1)
     sc = np.zeros(nb, np.uint8)
     assert lib.qo_pair_losses(C.cast(jobs, C.c_void_p), 2, sc.ctypes.data, nb, None) == 0
     r1, r2, q1, q2 = np.zeros_like(p), np.zeros_like(est), np.zeros(1, np.float32), np.zeros(1, np.float32)
-    lib.qo_pair_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     assert lib.qo_pair_loss(p.ctypes.data, h.ctypes.data, rows, 29, 29, 0, r1.ctypes.data, q1.ctypes.data, None, 0, None) == 0
     assert lib.qo_pair_loss(est.ctypes.data, wide.ctypes.data + 28, rows, 4, 53, 1, r2.ctypes.data, q2.ctypes.data, None, 0, None) == 0
     assert o1[0] == q1[0] and o2[0] == q2[0] and np.array_equal(g1, r1 * coef[0]) and np.array_equal(g2, r2)
@@ -951,7 +929,6 @@ def _stack_case(seed=0):
 def _run_stack(lib, prefix, T, to_dev, ticket_ptr, stream):
     from quadrupedal_agility_amd._capi import QaAdamStackTensor
     fn = getattr(lib, prefix + "adam_stack_step")
-    fn.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     recs = (QaAdamStackTensor * len(T))()
     dev = []
     for i, t in enumerate(T):
@@ -1014,7 +991,6 @@ def test_accumulate_scalars_is_stack_and_add():
 
 def test_accumulate_scalars_twin():
     lib = load_oracle()
-    lib.qo_accumulate_scalars.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     acc = np.arange(4, dtype=np.float32)
     xs = [np.array([v], np.float32) for v in (0.5, -1.0, 2.0)]
     ptrs = (C.c_void_p * 3)(*[x.ctypes.data for x in xs])

@@ -27,7 +27,6 @@ def _cases(seed=0):
 
 def test_grad_reduce_twin_matches_numpy():
     lib = load_oracle()
-    lib.qo_grad_reduce.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]
     shapes, src = _cases()
     dst = [np.zeros(n, np.float32) for n, _ in shapes]
     stride = np.array([n + 3 for n, _ in shapes], np.int64); parts = np.array([p for _, p in shapes], np.int32); numel = np.array([n for n, _ in shapes], np.int32)

@@ -81,7 +81,6 @@ def test_rollout_post_amp_twin():
     a = [np.ascontiguousarray(x.numpy()) for x in (rew, reset, tout, values, d, eps, logits, obs)]
     st_r, st_d = np.zeros(n, np.float32), np.zeros(n, np.uint8)
     cur_n, fin, mask = cur.numpy().copy(), np.zeros((6, n), np.float32), np.zeros(n, np.uint8)
-    qo.qo_rollout_post_amp.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_void_p, C.c_int64, C.c_int32] + [C.c_float] * 6 + [C.c_int32] + [C.c_void_p] * 6
     assert qo.qo_rollout_post_amp(*[P(x) for x in a[:7]], dim_c, P(a[7]), stride, num_obs, ci, cus, css, ct, dt, gamma, n,
                                   P(st_r), P(st_d), P(cur_n), P(fin), P(mask), None) == 0
     np.testing.assert_allclose(st_r, (total + gamma * values * tout.float()).numpy(), rtol=2e-5, atol=2e-6)
@@ -100,7 +99,6 @@ def test_hybrid_ppo_loss_twin_matches_the_eager_objective_and_its_autograd_gradi
     from tests.oracle_lib import load_oracle
     lib = load_oracle()
     f = lib.qo_hybrid_ppo_loss
-    f.argtypes = [C.c_void_p] * 12 + [C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]
     torch.manual_seed(3)
     B, ND, NC, clip, cv, ce = 777, 3, 18, 0.2, 1.0, 0.01
     logits = (torch.randn(B, ND) * 2).requires_grad_(True)

@@ -48,9 +48,7 @@ def render(fn, cfg, root, pitch, hmap, cmap, ep_len, buf, stream=None, coarse=No
 
 
 def oracle_fn():
-    lib = load_oracle()
-    f = lib.qo_tsc_depth_update; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; f.restype = C.c_int
-    return f
+    return load_oracle().qo_tsc_depth_update
 
 
 def scene(n=1, rows=200, cols=200, z=0.35, yaw=0.0):

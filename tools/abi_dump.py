@@ -1,0 +1,96 @@
+#!/usr/bin/env python
+"""The ctypes layer of quadrupedal_agility_amd/_capi.py as one canonical JSON: what Python believes the C ABI of include/*.h to be.
+
+    python tools/abi_dump.py            print it
+    python tools/abi_dump.py --write    regenerate tests/golden/abi.json (after a deliberate change of a header)
+    python tools/abi_dump.py --check    exit 1 and print the differing keys when it is not tests/golden/abi.json
+
+tests/test_abi.py compares the two.  Only _capi's public surface is read (load_library, ABI_SYMBOLS, EXTENSION_SYMBOLS, its Structure
+classes and its constants), so the same file describes any commit's binding, however that commit builds it.  It holds
+  functions   for every bound entry point the list that names it (ABI_SYMBOLS or EXTENSION_SYMBOLS: sets, their order means nothing and is not
+              kept), its restype and per-argument kind: ptr, i32, i64, u32, u64, f32, f64 (restype also str); args null = argtypes never set
+              (qa_last_error, qa_abi_version: no arguments, restype only)
+  structs     for every ctypes.Structure of _capi each field's name, offset, size and type, and the total size
+  constants   every public int, float, str, list, tuple and dict (with the container's type: a tuple is not a list)
+LIB_PATH is left out: it is where this checkout lies, not part of the ABI."""
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "abi.json")
+SCALARS = {C.c_int32: "i32", C.c_int64: "i64", C.c_uint32: "u32", C.c_uint64: "u64", C.c_float: "f32", C.c_double: "f64"}
+
+
+def kind(t):
+    """the kind of an argument or return type"""
+    if t in SCALARS:
+        return SCALARS[t]
+    if t is C.c_char_p:
+        return "str"
+    if t is C.c_void_p or issubclass(t, (C._Pointer, C.Array)):
+        return "ptr"
+    raise TypeError(f"no kind for {t!r}")
+
+
+def type_name(t):
+    """the type of a struct field: a scalar kind, ptr, a struct's name, or one of those with [n] per array dimension"""
+    if issubclass(t, C.Array):
+        dims = ""
+        while issubclass(t, C.Array):
+            dims, t = dims + f"[{t._length_}]", t._type_
+        return type_name(t) + dims
+    return t.__name__ if issubclass(t, C.Structure) else kind(t)
+
+
+def dump():
+    sys.path.insert(0, ROOT)
+    from quadrupedal_agility_amd import _capi
+    lib = _capi.load_library()
+    functions = {}
+    symbols = [(name, which) for which in ("ABI_SYMBOLS", "EXTENSION_SYMBOLS") for name in getattr(_capi, which)]
+    assert len(set(name for name, _ in symbols)) == len(symbols), "a symbol is listed twice"
+    for name, which in symbols:
+        f = getattr(lib, "qa_" + name)
+        functions[name] = {"list": which, "restype": kind(f.restype),
+                           "args": None if f.argtypes is None else ["ptr" if kind(t) == "str" else kind(t) for t in f.argtypes]}
+    structs, constants = {}, {}
+    for name, v in vars(_capi).items():
+        if name.startswith("_") or name in ("LIB_PATH", "ABI_SYMBOLS", "EXTENSION_SYMBOLS"):
+            continue
+        if isinstance(v, type) and issubclass(v, C.Structure):
+            structs[name] = {"size": C.sizeof(v), "fields": [{"name": f, "offset": getattr(v, f).offset, "size": getattr(v, f).size, "type": type_name(t)}
+                                                             for f, t in v._fields_]}
+        elif isinstance(v, (int, float, str)) and not isinstance(v, bool):
+            constants[name] = v
+        elif isinstance(v, (list, tuple)):
+            constants[name] = {type(v).__name__: list(v)}
+        elif isinstance(v, dict):
+            constants[name] = {"dict": [[k, x] for k, x in v.items()]}
+    return {"functions": functions, "structs": structs, "constants": constants}
+
+
+def text(d):
+    return json.dumps(d, indent=1, sort_keys=True) + "\n"
+
+
+def differences(a, b, path=""):
+    """the paths at which two dumps differ"""
+    if isinstance(a, dict) and isinstance(b, dict):
+        return [p for k in sorted(set(a) | set(b)) for p in
+                ([f"{path}/{k}: only in one"] if (k in a) != (k in b) else differences(a[k], b[k], f"{path}/{k}"))]
+    return [] if a == b else [f"{path}: {a!r} != {b!r}"]
+
+
+if __name__ == "__main__":
+    d = dump()
+    if "--write" in sys.argv:
+        with open(GOLDEN, "w") as f:
+            f.write(text(d))
+    elif "--check" in sys.argv:
+        diff = differences(d, json.load(open(GOLDEN)))
+        print("\n".join(diff) if diff else "equal to tests/golden/abi.json")
+        sys.exit(1 if diff else 0)
+    else:
+        sys.stdout.write(text(d))
