@@ -10,7 +10,8 @@
  *   terrain_type 0   the plane z = 0
  *   terrain_type 1   the height field's two-triangle cell surface with the clamped lookup of collision and of the depth camera (outside the
  *                    map the border's edge continues), plus the ceiling map where given; a ceiling triangle with a QA_NO_CEILING corner
- *                    does not exist.  The articulated obstacles are drawn as built (the static maps), not in their joint state.
+ *                    does not exist.  The articulated obstacles are drawn as built (the static maps); in their joint state, and with the
+ *                    env's goals, by the course mode of qa_render_course.h (QA_RENDER_COURSE in `flags`).
  * Pinhole camera: eye, target, vertical field of view; up = +z (a camera looking straight up or down takes +x as up).  Pixel (i, j) looks
  * through ((j + 0.5) / width, (i + 0.5) / height) of the image plane, row 0 at the top.
  * Shading: a fixed colour per class (trunk, hip, thigh, calf, foot, ground, ceiling, sky) x (ambient + (1 - ambient) max(0, n.l)); the

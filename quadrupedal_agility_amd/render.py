@@ -15,9 +15,14 @@ import zlib
 import torch
 
 from . import _capi
+from . import _cdecl
 
 DEFAULT_LIGHT = (0.35, 0.25, 1.0)
 DEFAULT_FAR = 30.0
+# include/qa_render_course.h: constants and one struct, no entry point -- read from the headers directly, _capi's public names stay as they are
+QaRenderCourse = _cdecl.struct("qa_render_course")
+RENDER_COURSE, RENDER_MAX_GOALS = _cdecl.values("QA_RENDER_", "COURSE MAX_GOALS")
+DEFAULT_GOAL_RADIUS = 0.1               # the reference viewer's goal spheres (tsc legged_robot.py _draw_goals)
 
 
 def _check(t, name, dtype, shape, device=None):
@@ -31,11 +36,15 @@ def _check(t, name, dtype, shape, device=None):
 
 def render_frames(body_state, env_ids, cameras, rgb, depth=None, ids=None, height_samples=None, ceiling_samples=None, border_size=0.0,
                   horizontal_scale=0.0, vertical_scale=0.0, far=DEFAULT_FAR, light_dir=DEFAULT_LIGHT, shadows=True, checker=True,
-                  env_ids_host=None, api=None):
+                  env_ids_host=None, api=None, obst_desc=None, obst_state=None, goals=None, cur_goal_idx=None, reached=None,
+                  goal_radius=DEFAULT_GOAL_RADIUS):
     """qa_render_frames on the current stream of `rgb`'s device.  body_state (N,19,13) fp32 (the engine's live RIGID_BODY_STATE), env_ids (K)
     int32, cameras (K,7) fp32 [eye, target, vertical fov in radians], rgb (K,H,W,3) uint8; optional depth (K,H,W) fp32 and ids (K,H,W) int8.
     `height_samples` (rows, cols) int16 selects the height field (else the plane z = 0), `ceiling_samples` the same grid.  `env_ids_host`: a
-    CPU copy of env_ids; with it an entry outside [0, N) is refused, without it the kernel clamps."""
+    CPU copy of env_ids; with it an entry outside [0, N) is refused, without it the kernel clamps.
+    The course mode (include/qa_render_course.h; height field only): `obst_desc` (N,3,8) / `obst_state` (N,3,4) fp32, the env's live OBST_DESC
+    and OBST_STATE, draw see-saw, bar and tyre in their joint state; `goals` (N,G,3) fp32 draws spheres of `goal_radius`, `cur_goal_idx` (N)
+    int64 and `reached` (N) uint8 colour the current one.  All are read when the launch executes."""
     dev = rgb.device if torch.is_tensor(rgb) else None
     if not torch.is_tensor(rgb) or rgb.dim() != 4 or rgb.shape[3] != 3:
         raise ValueError("render_frames: rgb must be a (K,H,W,3) uint8 tensor")
@@ -75,7 +84,36 @@ def render_frames(body_state, env_ids, cameras, rgb, depth=None, ids=None, heigh
     io.body_state, io.env_ids, io.cameras, io.rgb = body_state.data_ptr(), env_ids.data_ptr(), cameras.data_ptr(), rgb.data_ptr()
     io.depth = depth.data_ptr() if depth is not None else None
     io.ids = ids.data_ptr() if ids is not None else None
-    (api or _capi.API).launch("render_frames", C.byref(cfg), C.byref(io), on=rgb)
+    if all(v is None for v in (obst_desc, obst_state, goals, cur_goal_idx, reached)):
+        (api or _capi.API).launch("render_frames", C.byref(cfg), C.byref(io), on=rgb)
+        return rgb
+    if height_samples is None:
+        raise ValueError("render_frames: obstacles and goals are drawn on the height field: height_samples is required")
+    if (obst_desc is None) != (obst_state is None):
+        raise ValueError("render_frames: obst_desc and obst_state go together")
+    if goals is None and (cur_goal_idx is not None or reached is not None):
+        raise ValueError("render_frames: cur_goal_idx / reached without goals")
+    course = QaRenderCourse()
+    course.io = io
+    if obst_desc is not None:
+        _check(obst_desc, "obst_desc", torch.float32, (N, 3, 8), dev)
+        _check(obst_state, "obst_state", torch.float32, (N, 3, 4), dev)
+        course.obst_desc, course.obst_state = obst_desc.data_ptr(), obst_state.data_ptr()
+    if goals is not None:
+        if not torch.is_tensor(goals) or goals.dim() != 3 or not 1 <= int(goals.shape[1]) <= RENDER_MAX_GOALS:
+            raise ValueError(f"render_frames: goals must be a (N,G,3) float32 tensor with 1 <= G <= {RENDER_MAX_GOALS}")
+        _check(goals, "goals", torch.float32, (N, int(goals.shape[1]), 3), dev)
+        if not float(goal_radius) > 0.0:
+            raise ValueError(f"render_frames: goal_radius = {goal_radius}")
+        course.goals, course.num_goals, course.goal_radius = goals.data_ptr(), int(goals.shape[1]), float(goal_radius)
+        if cur_goal_idx is not None:
+            _check(cur_goal_idx, "cur_goal_idx", torch.int64, (N,), dev)
+            course.cur_goal_idx = cur_goal_idx.data_ptr()
+        if reached is not None:
+            _check(reached, "reached", torch.uint8, (N,), dev)
+            course.reached = reached.data_ptr()
+    cfg.flags |= RENDER_COURSE
+    (api or _capi.API).launch("render_frames", C.byref(cfg), C.byref(course), on=rgb)
     return rgb
 
 
@@ -129,7 +167,8 @@ class FrameRecorder:
     to the host and writes <out_dir>/<img_idx>.png (one env) or <out_dir>/env<id>/<img_idx>.png (several)."""
 
     def __init__(self, env, out_dir, env_ids=(0,), size=(640, 360), every=2, camera="follow", offset=(-2.8, -1.8, 1.8), fov_deg=60.0,
-                 eye=None, target=None, far=DEFAULT_FAR, light_dir=DEFAULT_LIGHT, shadows=True, checker=True, with_ids=False):
+                 eye=None, target=None, far=DEFAULT_FAR, light_dir=DEFAULT_LIGHT, shadows=True, checker=True, with_ids=False,
+                 articulated=False, goals=False, goal_radius=DEFAULT_GOAL_RADIUS):
         sim = env.sim
         q = sim.cfg
         if not int(q.export_body_state):
@@ -164,6 +203,17 @@ class FrameRecorder:
             self._terrain = dict(height_samples=sim.t["HEIGHT_SAMPLES"], border_size=float(q.hf_border), horizontal_scale=float(q.hf_hscale),
                                  vertical_scale=float(q.hf_vscale), ceiling_samples=sim.t["CEILING_SAMPLES"] if int(q.hf_ceiling) else None)
         self._opts = dict(far=far, light_dir=light_dir, shadows=shadows, checker=checker)
+        # the course as the physics has it and the goals (include/qa_render_course.h): the env's own live tensors, nothing is copied
+        if articulated:
+            if not getattr(env, "articulated", False):
+                raise ValueError("FrameRecorder: articulated=True needs an env whose see-saw, bar and tyre are articulated bodies "
+                                 "(the task-level tree with articulated_obstacles): this env keeps the static maps")
+            self._opts.update(obst_desc=sim.t["OBST_DESC"], obst_state=env.obst_state)
+        if goals:
+            bk = getattr(env, "bk", None)
+            if not hasattr(env, "env_goals") or bk is None:
+                raise ValueError("FrameRecorder: goals=True needs an env with goals (the task-level tree's env_goals and goal bookkeeping)")
+            self._opts.update(goals=env.env_goals, cur_goal_idx=bk.cur_goal_idx, reached=bk.reached_goal_ids, goal_radius=goal_radius)
         self._api = sim.api
         self.img_idx = 0
 
@@ -201,6 +251,9 @@ def add_record_args(parser):
     parser.add_argument("--record_offset", type=str, default=None, metavar="X,Y,Z",
                         help="the follow camera's eye relative to the robot's root, world axes (default: the reference's camera_pos_bias -2.8,-1.8,1.8; "
                              "on the obstacle course 0,-1.2,2.6, inside the lane's 2 m walls)")
+    parser.add_argument("--record_articulated", action="store_true", default=False,
+                        help="draw see-saw, bar and tyre in their joint state, as the physics has them (the task-level tree with articulated obstacles)")
+    parser.add_argument("--record_goals", action="store_true", default=False, help="draw the env's goals as spheres: red, the current one blue, green once reached")
 
 
 COURSE_OFFSET = (0.0, -1.2, 2.6)       # the course's lanes run along +y between 2 m walls: the reference's bias would put the eye behind one
@@ -224,4 +277,7 @@ def record_settings(args, experiment_name, default_offset=None):
     out = dict(out_dir=out_dir, env_ids=env_ids, size=(w, h), every=int(getattr(args, "record_every", 2)))
     if offset is not None:
         out["offset"] = offset
+    for flag, key in (("record_articulated", "articulated"), ("record_goals", "goals")):
+        if getattr(args, flag, False):
+            out[key] = True
     return out

@@ -3,7 +3,8 @@ deployment loop -- estimator -> (depth encoder -> student actor | teacher actor)
 env.step -- for `--num_steps` steps; prints and returns the course success rate (`reach_goal` of the finished episodes).
 `python -m quadrupedal_agility_amd.tsc.legged_gym.scripts.play --task go2 --exptid <run> [--use_camera] [--num_steps N]`
 `--record_frames [DIR]` (the reference's RECORD_FRAMES, :135): every `--record_every`-th step a HIP ray-cast of the robot over the course's
-floor and ceiling maps is written to DIR/<n>.png (default logs/<experiment_name>/exported/frames); quadrupedal_agility_amd/render.py."""
+floor and ceiling maps is written to DIR/<n>.png (default logs/<experiment_name>/exported/frames); quadrupedal_agility_amd/render.py.
+`--record_articulated` draws see-saw, bar and tyre in their joint state instead of as built, `--record_goals` the env's goals."""
 import statistics
 from collections import deque
 
