@@ -885,6 +885,14 @@ static int pick_cfg(int64_t a_count, int64_t b_count, int64_t nsplit) {
 }
 
 static int g_force_cfg = -1;      // tools/gemm_bench.py: time one tile configuration
+// The forced tile as the LINEAR entry points see it -- the one place planning (wgrad_plan), *_scratch_bytes / *_layout and the launch read it, so
+// that they agree on the a-tile count of the bias slabs: 0..3 and 10..14 name a linear tile; 4..9 name none (4 is the window GEMMs' 32 x 128)
+// and run as 64 x 64; anything outside every table is no force at all.
+static int linear_force_cfg() {
+    const int f = g_force_cfg;
+    if (f < 0 || f > 14) return -1;
+    return (f >= 4 && f <= 9) ? 2 : f;
+}
 
 // QA_GEMM_DMA: 1 = products that qualify (dma_ok) take the LDS-DMA kernel with the tile chosen below, 0 = register-staged kernel only
 static int dma_mode() {
@@ -922,7 +930,8 @@ int qa_linear_forward(const float *x, int64_t ldx, const float *weight, int64_t 
     g.a_vec = (aligned16(weight) && ldw % 4 == 0 && in_features % 4 == 0) ? 4 : 1;
     g.b_vec = (aligned16(x) && ldx % 4 == 0 && in_features % 4 == 0) ? 4 : 1;
     g.o_vec = (aligned16(y) && ldy % 4 == 0 && (!bias || aligned16(bias))) ? 4 : 1;
-    gemm_launch<false, false, 1, false>(g_force_cfg >= 0 ? g_force_cfg : ((dma_mode() && dma_ok(g, false, false)) ? pick_cfg_dma(out_features, rows, 1) : pick_cfg(out_features, rows, 1)),
+    const int forced = linear_force_cfg();
+    gemm_launch<false, false, 1, false>(forced >= 0 ? forced : ((dma_mode() && dma_ok(g, false, false)) ? pick_cfg_dma(out_features, rows, 1) : pick_cfg(out_features, rows, 1)),
                                          g, (hipStream_t)stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_gerr, sizeof(g_gerr), "qa_linear_forward: %s", hipGetErrorString(e)); return QA_E_DEVICE; }
@@ -944,7 +953,8 @@ int qa_linear_backward_input(const float *grad_out, int64_t ldg, const float *we
     g.a_vec = (aligned16(weight) && ldw % 4 == 0 && in_features % 4 == 0) ? 4 : 1;
     g.b_vec = (aligned16(grad_out) && ldg % 4 == 0 && out_features % 4 == 0) ? 4 : 1;
     g.o_vec = (aligned16(grad_in) && ldgi % 4 == 0 && (!g.yprev || (aligned16(y_prev) && ldyp % 4 == 0))) ? 4 : 1;
-    gemm_launch<true, false, 2, false>(g_force_cfg >= 0 ? g_force_cfg : ((dma_mode() && dma_ok(g, true, false)) ? pick_cfg_dma(in_features, rows, 1) : pick_cfg(in_features, rows, 1)),
+    const int forced = linear_force_cfg();
+    gemm_launch<true, false, 2, false>(forced >= 0 ? forced : ((dma_mode() && dma_ok(g, true, false)) ? pick_cfg_dma(in_features, rows, 1) : pick_cfg(in_features, rows, 1)),
                                         g, (hipStream_t)stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_gerr, sizeof(g_gerr), "qa_linear_backward_input: %s", hipGetErrorString(e)); return QA_E_DEVICE; }
@@ -958,7 +968,8 @@ static void wgrad_plan(int64_t rows, int32_t in_features, int32_t out_features, 
     int c = (in_features > 256 && out_features > 256) ? 0 : ((in_features >= 256 && out_features >= 128) ? 1 : 2);
     if (dma_mode() && rows % GEMM_BK == 0 && in_features % 4 == 0 && out_features % 4 == 0)        // (alignment of the operands is checked at launch: dma_ok)
         c = (in_features > 256 && out_features > 256) ? 11 : ((in_features >= 128 && out_features >= 64) ? 12 : 13);
-    if (g_force_cfg >= 0) c = g_force_cfg;
+    const int forced = linear_force_cfg();
+    if (forced >= 0) c = forced;
     int ba, bb; tile_dims(c, &ba, &bb);
     const int64_t tiles = (int64_t)((in_features + ba - 1) / ba) * ((out_features + bb - 1) / bb);
     // resident workgroups: 2 per CU for the 128 x 128 tile (190-200 registers), 4 otherwise; LDS-DMA tiles: 2 (128 x 192: 60 KB of LDS), 3 (48 KB), 4
@@ -1265,7 +1276,8 @@ int qa_linear_forward_split(const float *x, int64_t ldx, const float *weight, in
     g.b_vec = (aligned16(x) && ldx % 4 == 0 && in_features % 4 == 0) ? 4 : 1;
     g.o_vec = 4;
     hipStream_t st = (hipStream_t)stream;
-    gemm_launch<false, false, 0, false>(g_force_cfg >= 0 ? g_force_cfg : 2, g, st);
+    const int forced = linear_force_cfg();
+    gemm_launch<false, false, 0, false>(forced >= 0 ? forced : 2, g, st);
     const int64_t nthreads = rows * (out_features / 4);
     hipLaunchKernelGGL(qa_slab_bias_act_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, st, (const float *)scratch, n_pad, s, rows,
                        (int)out_features, bias, (int)act, alpha, y, ldy);
