@@ -575,7 +575,9 @@ int qa_clip_adam_step_hostgrads(float *const *params, const float *const *grads_
 /* r5 (ABI 14): the same step for gradients that are still IN PARTS.  The weight gradient of a Linear layer leaves its split-K product as S
  * slabs (gail.py:328-413's backward through `torch.mm`; here fused.weight_grad's batched product) and its bias gradient leaves
  * qa_elu_backward_bias as one row of column sums per 64-row block: tensor t with red_parts_host[t] > 0 is
- *     grad[t][i] = sum_z red_src_host[t][z * red_stride_host[t] + i],  z = 0 .. parts - 1 in order (bit-reproducible)
+ *     grad[t][i] = sum_z red_src_host[t][z * red_stride_host[t] + i]   in a fixed order (bit-reproducible): z = 0 .. parts - 1 ascending for up to 16
+ *     parts; for more, the order of the column-sum finish -- eight lanes, lane q adds parts q, q + 8, ... (32 at a time into four accumulators while
+ *     more than 24 remain, summed (a0 + a1) + (a2 + a3)), then the lanes are added in lane order
  * and the sums-of-squares pass of the step adds the parts, WRITES the result to grads_host[t] (so whatever reads `.grad` after the step sees
  * the finished gradient) and squares it: the ~19 fixed-order finish launches of a PPO minibatch step (qa_colsum_finish, qa_slab_reduce) are
  * not made.  red_parts_host[t] == 0: the gradient is already final.  All three red_* arrays are HOST arrays of num_tensors entries
@@ -605,7 +607,7 @@ int qa_clip_adam_pair_step(float *const *params, const float *const *grads_host,
                            float beta2, float eps, float max_norm, float *scratch, int64_t scratch_floats,
                            const float *const *red_src_host, const int64_t *red_stride_host, const int32_t *red_parts_host, const qa_adam_pair *pair, void *stream);
 /* The parts of up to QA_ADAM_MAX_INLINE gradients added in ONE launch without an optimiser step (the data-parallel step packs finished
- * gradients into its all-reduce bucket; tests): dst_host[t][i] = sum_z src_host[t][z stride_host[t] + i], i < numel_host[t]. */
+ * gradients into its all-reduce bucket; tests): dst_host[t][i] = sum_z src_host[t][z stride_host[t] + i], i < numel_host[t], in the same two fixed orders. */
 int qa_grad_reduce(float *const *dst_host, const float *const *src_host, const int64_t *stride_host, const int32_t *parts_host,
                    const int32_t *numel_host, int32_t num_tensors, void *stream);
 

@@ -1874,9 +1874,9 @@ int qo_normalizer_update(const float *const *batches, const int64_t *rows, int32
                          double *mean, double *var, double *count, void *stream) {
     (void)stream;
     if (!batches || !rows || !mean || !var || !count || num_batches <= 0 || num_batches > 4 || dim <= 0 || dim > 128) return QA_E_ARG;
+    for (int b = 0; b < num_batches; ++b) if (!batches[b] || rows[b] <= 0) return QA_E_ARG;      /* before any batch is merged, as the kernel's entry point */
     for (int b = 0; b < num_batches; ++b) {
         const float *x = batches[b]; int64_t n = rows[b];
-        if (!x || n <= 0) return QA_E_ARG;
         double total = *count + (double)n;
         for (int c = 0; c < dim; ++c) {
             double bm = 0, bv = 0;
@@ -1915,7 +1915,8 @@ int qo_clip_adam_step(float *const *params, const float *const *grads, float *co
         !scratch || num_tensors <= 0 || num_chunks <= 0 || scratch_floats < 4 + (int64_t)num_chunks) return QA_E_ARG;
     double ss = 0;
     for (int c = 0; c < num_chunks; ++c) { const float *g = grads[chunk_tensor[c]] + chunk_start[c]; for (int i = 0; i < chunk_len[c]; ++i) ss += (double)g[i] * g[i]; }
-    float norm = (float)sqrt(ss), coef = max_norm > 0.0f ? fminf(1.0f, max_norm / (norm + 1e-6f)) : 1.0f;
+    float norm = max_norm > 0.0f ? (float)sqrt(ss) : 0.0f;        /* reported as 0 without clipping, as include/qa_sim.h says and the kernels do */
+    float coef = max_norm > 0.0f ? fminf(1.0f, max_norm / (norm + 1e-6f)) : 1.0f;
     float step = steps[0][0] + 1.0f;
     for (int t = 0; t < num_tensors; ++t) steps[t][0] = step;
     float bc1 = 1.0f - powf(beta1, step), bc2s = sqrtf(1.0f - powf(beta2, step)), step_size = lr[0] / bc1;

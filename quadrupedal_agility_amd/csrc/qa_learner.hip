@@ -557,8 +557,8 @@ struct AdamArgs {
 };
 __device__ __forceinline__ const float *adam_grad(const AdamArgs &a, int t) { return a.inline_grads ? a.gin[t] : a.grads[t]; }
 
-// one chunk of a gradient that is still in parts: element i = sum_z src[z stride + i], z ascending (bit-reproducible), written to g and
-// returned squared-and-summed per thread.  Few parts (split-K slabs, <= QA_REDUCE_WIDE): a thread owns elements tid, tid + 256, ...; many
+// one chunk of a gradient that is still in parts: element i = sum_z src[z stride + i] in a fixed order (bit-reproducible: z ascending for few parts,
+// the column-sum finish's eight-lane order for many), written to g and returned squared-and-summed per thread.  Few parts (split-K slabs, <= QA_REDUCE_WIDE): a thread owns elements tid, tid + 256, ...; many
 // parts (column partials of 24,576 / 64 = 384 row blocks): the chunk is <= 32 elements wide (the host's chunk table guarantees it for
 // every tensor that can carry such parts) and the 8 thread rows of 32 share the parts like qa_colsum_finish_kernel does.
 constexpr int QA_REDUCE_WIDE = 16;
