@@ -3,12 +3,14 @@
 Only CUDA/ROCm tensors come here: the callers keep the plain PyTorch expression for CPU tensors (BASELINE config 1,
 "PPO on CPU physics + CPU torch"), which is also the fp32 reference the kernels are tested against."""
 import ctypes as C
+import functools
 import os
 
 import torch
 
 from quadrupedal_agility_amd import _capi
 from quadrupedal_agility_amd._capi import API, _ptr
+from quadrupedal_agility_amd.rsl_rl.algorithms import mlp_program
 
 
 ENABLED = True      # tests flip this to compare against the unfused modules
@@ -1364,6 +1366,23 @@ def gae(rewards, values, dones, last_values, returns, advantages, gamma, lam, no
                float(lam), int(bool(normalize)), _ptr(scratch), on=rewards)
 
 
+def _none_on_misfit(describe):
+    """a description the kernel's rule does not admit (mlp_program.Misfit) is declined: None, and the caller keeps the modules"""
+    @functools.wraps(describe)
+    def declining(*args, **kwargs):
+        try:
+            return describe(*args, **kwargs)
+        except mlp_program.Misfit:
+            return None
+    return declining
+
+
+def _ends_in(layers, n):
+    """the width a description's columns assume of a stack's last layer"""
+    if layers[-1][0].out_features != n:
+        raise mlp_program.Misfit("width", layers[-1][0].out_features, n)
+
+
 class PolicyChain:
     """SSInfoGAIL.act's network half -- Estimator.forward, the privileged-latent encoder, the actor trunk + head and the
     critic trunk + head (gail.py:176-197) -- as ONE launch: `qa_mlp_forward` carries each 16-row tile through every
@@ -1375,22 +1394,18 @@ class PolicyChain:
 
     BUF_COLS = _capi.MLP_BUF_COLS
 
-    def __init__(self, ops, params, num_actions, out_widths=None):
-        self.n_ops = len(ops)
-        self.ops = (_capi.QaMlpOp * self.n_ops)(*ops)
-        self.params = params                      # per op: (weight, bias) tensors (or callables building them) or None
+    def __init__(self, prog, num_actions, out_widths=None):
+        self._prog = prog.seal()                  # the op list, written through mlp_program.Program
+        self.ops, self.n_ops = prog.c_ops, prog.n_ops
+        self.params = prog.params                 # per op: (weight, bias) tensors (or callables building them) or None
+        self.packed_floats = prog.woff
         self.num_actions = num_actions
         self.out_widths = list(out_widths) if out_widths is not None else [num_actions, 1]
         self.packed = None
         self._out = {}
 
     # ---------------------------------------------------------------- description (host logic, no device access)
-    @staticmethod
-    def k_blocks(k, n):
-        """16-wide k-blocks a layer is stored with (qa_policy.hip mlp_kb): rounded up to the kernel's prefetch depth"""
-        per = ((n + 15) // 16 + 7) // 8
-        pf = 4 if per > 2 else 8
-        return ((k + 15) // 16 + pf - 1) // pf * pf
+    k_blocks = staticmethod(mlp_program.k_blocks)
 
     @staticmethod
     def _linears(seq, table=False):
@@ -1413,37 +1428,26 @@ class PolicyChain:
         return out
 
     @classmethod
+    @_none_on_misfit
     def describe_discriminator(cls, disc):
         """Discriminator.forward (bbc/rsl_rl/algorithms/discriminator.py:48-69) on prepared inputs x (N, 98): ReLU trunk, then the
         three heads as global outputs (logit (N,1), epsilon (N,1), class LOGITS (N,dim_c): the softmax is the consumer's)."""
         trunk = cls._linears(disc.trunk)
         if trunk is None or any(a != 2 for _, a in trunk) or disc.input_dim > cls.BUF_COLS[0] or disc.dim_c > 8:
             return None
-        ops, params, woff, src, scol, k = [], [], 0, 0, 0, disc.input_dim
-        bufs = {0: 1, 1: 2, 2: 1}
+        p, src, k = mlp_program.Program(), 0, disc.input_dim
         for lin, act in trunk:
-            dst = bufs[src]
-            n = lin.out_features
-            if lin.in_features != k or n > cls.BUF_COLS[dst]:
+            if lin.in_features != k:
                 return None
-            nt, kb = (n + 15) // 16, cls.k_blocks(k, n)
-            ops.append(_capi.QaMlpOp(kind=_capi.MLP_LAYER, src_buf=src, src_col=0, dst_buf=dst, dst_col=0, k=k, n=n, act=act, out_index=0,
-                                     w_off=woff, b_off=woff + nt * kb * 256))
-            params.append((lin.weight, lin.bias))
-            woff += nt * kb * 256 + nt * 16
-            src, k = dst, n
+            dst = 2 if src == 1 else 1
+            p.layer(src, 0, k, dst, 0, lin.out_features, act, lin.weight, lin.bias)
+            src, k = dst, lin.out_features
         for oi, head in enumerate((disc.linear, disc.encoder_eps, disc.classifier)):
-            n = head.out_features
-            nt, kb = (n + 15) // 16, cls.k_blocks(k, n)
-            ops.append(_capi.QaMlpOp(kind=_capi.MLP_LAYER, src_buf=src, src_col=0, dst_buf=-1, dst_col=0, k=k, n=n, act=0, out_index=oi,
-                                     w_off=woff, b_off=woff + nt * kb * 256))
-            params.append((head.weight, head.bias))
-            woff += nt * kb * 256 + nt * 16
-        self = cls(ops, params, 0, out_widths=[1, 1, disc.dim_c])
-        self.packed_floats = woff
-        return self
+            p.layer(src, 0, k, -1, 0, head.out_features, 0, head.weight, head.bias, out=(oi, 0))
+        return cls(p, 0, out_widths=[1, 1, disc.dim_c])
 
     @classmethod
+    @_none_on_misfit
     def describe(cls, actor_critic, estimator, use_estimator, hist_encoding=False, with_critic=True, estimate_col=None):
         """-> PolicyChain, or None when the modules are not plain Linear + activation stacks that fit the kernel's buffers (activations: the reference's
         table, ELU(alpha=1) and ReLU side by side or one other kind throughout -- `uniform_kinds`).
@@ -1479,46 +1483,8 @@ class PolicyChain:
         stacks["actor"] = stacks["actor"] + [[ac.actor_head, 0]]
         if with_critic:
             stacks["critic"] = stacks["critic"] + [[ac.critic_head, 0]]
-        ops, params, woff = [], [], [0]
+        p = mlp_program.Program()
         Z = 3
-        lds_end = sum(16 * (c + 4) for c in cls.BUF_COLS)
-
-        def copy(src, scol, dst, dcol, n):
-            ops.append(_capi.QaMlpOp(kind=_capi.MLP_COPY, src_buf=src, src_col=scol, dst_buf=dst, dst_col=dcol, k=0, n=n))
-            params.append(None)
-
-        def layer(src, scol, k, dst, dcol, n, act, oi, w, bias):
-            if dst == src or (dst >= 0 and dcol + n > cls.BUF_COLS[dst]) or scol % 4 or scol + k > cls.BUF_COLS[src] + 4:
-                return False
-            nt, kb = (n + 15) // 16, cls.k_blocks(k, n)
-            base = sum(16 * (c + 4) for c in cls.BUF_COLS[:src])
-            if base + 15 * (cls.BUF_COLS[src] + 4) + scol + 16 * kb > lds_end:
-                return False            # the padded k-blocks would be read from beyond the kernel's LDS
-            w_off = woff[0]; b_off = w_off + nt * kb * 256; woff[0] = b_off + nt * 16
-            ops.append(_capi.QaMlpOp(kind=_capi.MLP_LAYER, src_buf=src, src_col=scol, dst_buf=dst, dst_col=dcol, k=k, n=n, act=act,
-                                     out_index=oi, w_off=w_off, b_off=b_off))
-            params.append((w, bias))
-            return True
-
-        def chain(layers, src, scol, k, final, reserved):
-            """layers through scratch buffers; `final` = ("buf", b, col) or ("out", index)"""
-            for i, (lin, act) in enumerate(layers):
-                if lin.in_features != k:
-                    return False
-                n = lin.out_features
-                if i == len(layers) - 1:
-                    dst, dcol, oi = (final[1], final[2], 0) if final[0] == "buf" else (-1, 0, final[1])
-                else:
-                    fit = [b for b in (3, 2, 1) if b != src and b not in reserved and cls.BUF_COLS[b] >= n]
-                    if not fit:
-                        return False
-                    dst, dcol, oi = fit[0], 0, 0
-                if not layer(src, scol, k, dst, dcol, n, act, oi, lin.weight, lin.bias):
-                    return False
-                src, scol, k = dst, 0, n
-            return True
-
-        ok = True
         lat_col = n_prop + n_exp
         # estimate_col: where the estimator's output is written in the OBSERVATION row (default: the explicit privileged columns
         # right after proprio).  The task-level tree's act_bbc writes it at num_prop + num_scan of the 671-wide behaviour row
@@ -1555,35 +1521,36 @@ class PolicyChain:
                 return build
 
             rep = lambda b_, r: (lambda: b_.repeat(r))
-            copy(0, hist0, 1, 0, T * n_prop)
+            p.copy(0, hist0, 1, 0, T * n_prop)
             if est_in_obs:
-                ok &= chain(stacks["est"], 0, 0, n_prop, ("buf", 1, estimate_col - hist0), {1}) and stacks["est"][-1][0].out_features == n_exp
-            ok &= layer(1, 0, T * n_prop, 2, 0, T * C0, he_act, 0, lambda: torch.block_diag(*([enc.weight] * T)).contiguous(), rep(enc.bias, T))
-            ok &= layer(2, 0, T * C0, 3, 0, T1 * C1, he_act, 0, conv_matrix(c1, T, T1), rep(c1.bias, T1))
-            ok &= layer(3, 0, T1 * C1, 1, 0, T2 * C2, he_act, 0, conv_matrix(c2, T1, T2), rep(c2.bias, T2))
-            ok &= layer(1, 0, T2 * C2, Z, lat_col, n_lat, he_act, 0,
-                        lambda: outl.weight.view(n_lat, C2, T2).permute(0, 2, 1).reshape(n_lat, T2 * C2).contiguous(), outl.bias)
-        copy(0, 0, Z, 0, n_prop)
+                _ends_in(stacks["est"], n_exp)
+                p.stack(stacks["est"], 0, 0, n_prop, ("buf", 1, estimate_col - hist0), {1})
+            p.layer(1, 0, T * n_prop, 2, 0, T * C0, he_act, lambda: torch.block_diag(*([enc.weight] * T)).contiguous(), rep(enc.bias, T))
+            p.layer(2, 0, T * C0, 3, 0, T1 * C1, he_act, conv_matrix(c1, T, T1), rep(c1.bias, T1))
+            p.layer(3, 0, T1 * C1, 1, 0, T2 * C2, he_act, conv_matrix(c2, T1, T2), rep(c2.bias, T2))
+            p.layer(1, 0, T2 * C2, Z, lat_col, n_lat, he_act,
+                    lambda: outl.weight.view(n_lat, C2, T2).permute(0, 2, 1).reshape(n_lat, T2 * C2).contiguous(), outl.bias)
+        p.copy(0, 0, Z, 0, n_prop)
         if use_estimator and not est_in_obs:
-            ok &= chain(stacks["est"], 0, 0, n_prop, ("buf", Z, n_prop), {Z}) and stacks["est"][-1][0].out_features == n_exp
+            _ends_in(stacks["est"], n_exp)
+            p.stack(stacks["est"], 0, 0, n_prop, ("buf", Z, n_prop), {Z})
         else:
-            copy(0, n_prop, Z, n_prop, n_exp)
+            p.copy(0, n_prop, Z, n_prop, n_exp)
         if use_priv:
-            copy(0, lat_col, 2, 0, n_lat)                            # to column 0: a layer's source must be 16-byte aligned
-            ok &= chain(stacks["priv"], 2, 0, n_lat, ("buf", Z, lat_col), {Z}) and stacks["priv"][-1][0].out_features == n_lat
+            _ends_in(stacks["priv"], n_lat)
+            p.copy(0, lat_col, 2, 0, n_lat)                          # to column 0: a layer's source must be 16-byte aligned
+            p.stack(stacks["priv"], 2, 0, n_lat, ("buf", Z, lat_col), {Z})
         elif not use_hist:
-            copy(0, lat_col, Z, lat_col, n_lat)
-        copy(0, cmd0, Z, lat_col + n_lat, n_cmd)
-        ok &= chain(stacks["actor"], Z, 0, n_in, ("out", 0), set())
+            p.copy(0, lat_col, Z, lat_col, n_lat)
+        p.copy(0, cmd0, Z, lat_col + n_lat, n_cmd)
+        p.stack(stacks["actor"], Z, 0, n_in, ("out", 0))
         if with_critic:
-            ok &= chain(stacks["critic"], 0, 0, n_obs, ("out", 1), set()) and stacks["critic"][-1][0].out_features == 1
-        if not ok or len(ops) > _capi.MLP_MAX_OPS:
-            return None
-        self = cls(ops, params, stacks["actor"][-1][0].out_features)
-        self.packed_floats = woff[0]
-        return self
+            _ends_in(stacks["critic"], 1)
+            p.stack(stacks["critic"], 0, 0, n_obs, ("out", 1))
+        return cls(p, stacks["actor"][-1][0].out_features)
 
     @classmethod
+    @_none_on_misfit
     def describe_task_level(cls, actor_critic, estimator, use_estimator, part="all"):
         """The task-level teacher's networks of one env step (tsc/rsl_rl/algorithms/ppo.py:101-125 `act`: Estimator.forward on the first 57
         proprioception entries written over the privileged-explicit columns, Actor.forward -- scan encoder (last layer tanh), privileged
@@ -1622,89 +1589,39 @@ class PolicyChain:
         Z = 2                                               # the trunk's input is assembled in scratch buffer 2
         if n_obs > cls.BUF_COLS[0] or n_in > cls.BUF_COLS[Z] or st["trunk"][0][0].in_features != n_in or lat0 + n_lat > n_obs:
             return None
-        ops, params, woff = [], [], [0]
-        lds_end = sum(16 * (c + 4) for c in cls.BUF_COLS)
-
-        def copy(src, scol, dst, dcol, n):
-            ops.append(_capi.QaMlpOp(kind=_capi.MLP_COPY, src_buf=src, src_col=scol, dst_buf=dst, dst_col=dcol, k=0, n=n))
-            params.append(None)
-
-        def layer(src, scol, k, dst, dcol, n, act, oi, w, bias):
-            if dst == src or (dst >= 0 and dcol + n > cls.BUF_COLS[dst]) or scol % 4 or scol + k > cls.BUF_COLS[src] + 4:
-                return False
-            nt, kb = (n + 15) // 16, cls.k_blocks(k, n)
-            base = sum(16 * (c + 4) for c in cls.BUF_COLS[:src])
-            if base + 15 * (cls.BUF_COLS[src] + 4) + scol + 16 * kb > lds_end or nt > 32:
-                return False
-            w_off = woff[0]; b_off = w_off + nt * kb * 256; woff[0] = b_off + nt * 16
-            ops.append(_capi.QaMlpOp(kind=_capi.MLP_LAYER, src_buf=src, src_col=scol, dst_buf=dst, dst_col=dcol, k=k, n=n, act=act, out_index=oi, w_off=w_off, b_off=b_off))
-            params.append((w, bias))
-            return True
-
-        def chain(layers, src, scol, k, final, reserved):
-            for i, (lin, act) in enumerate(layers):
-                if lin.in_features != k:
-                    return False
-                n = lin.out_features
-                if i == len(layers) - 1:
-                    dst, dcol, oi = (final[1], final[2], 0) if final[0] == "buf" else (-1, 0, final[1])
-                else:
-                    fit = [b for b in (3, 2, 1) if b != src and b not in reserved and cls.BUF_COLS[b] >= n]
-                    if not fit:
-                        return False
-                    dst, dcol, oi = fit[0], 0, 0
-                if not layer(src, scol, k, dst, dcol, n, act, oi, lin.weight, lin.bias):
-                    return False
-                src, scol, k = dst, 0, n
-            return True
-
-        ok = st["critic"][-1][0].out_features == 1
+        _ends_in(crit, 1)
+        p = mlp_program.Program()
         if part != "actor":
-            ok = ok and chain(st["critic"], 0, 0, n_obs, ("out", 2 if part == "all" else 0), set())      # first: it may use every scratch buffer
+            p.stack(crit, 0, 0, n_obs, ("out", 2 if part == "all" else 0))      # first: it may use every scratch buffer
         if part == "critic":
-            if not ok or len(ops) > _capi.MLP_MAX_OPS:
-                return None
-            self = cls(ops, params, 1, out_widths=[1])
-            self.packed_floats = woff[0]
-            return self
-        copy(0, 0, Z, 0, a)
-        copy(0, scan0, 1, 0, n_scan)                        # a layer's source column must be 16-byte aligned: the scan starts at column 65
-        ok = ok and chain(st["scan"], 1, 0, n_scan, ("buf", Z, a), {Z})
+            return cls(p, 1, out_widths=[1])
+        p.copy(0, 0, Z, 0, a)
+        p.copy(0, scan0, 1, 0, n_scan)                      # a layer's source column must be 16-byte aligned: the scan starts at column 65
+        p.stack(st["scan"], 1, 0, n_scan, ("buf", Z, a), {Z})
         lat_dst = a + st["scan"][-1][0].out_features
         if use_estimator:
-            ok = ok and chain(st["est"], 0, 0, st["est"][0][0].in_features, ("buf", Z, lat_dst), {Z}) and st["est"][-1][0].out_features == n_exp
+            _ends_in(st["est"], n_exp)
+            p.stack(st["est"], 0, 0, st["est"][0][0].in_features, ("buf", Z, lat_dst), {Z})
         else:
-            copy(0, exp0, Z, lat_dst, n_exp)
-        copy(0, lat0, 1, 0, n_lat)
-        ok = ok and chain(st["priv"], 1, 0, n_lat, ("buf", Z, lat_dst + n_exp), {Z}) and st["priv"][-1][0].out_features == n_lat
-        ok = ok and chain(st["trunk"], Z, 0, n_in, ("buf", 3, 0), set())
+            p.copy(0, exp0, Z, lat_dst, n_exp)
+        p.copy(0, lat0, 1, 0, n_lat)
+        _ends_in(st["priv"], n_lat)
+        p.stack(st["priv"], 1, 0, n_lat, ("buf", Z, lat_dst + n_exp), {Z})
+        p.stack(st["trunk"], Z, 0, n_in, ("buf", 3, 0))
         k = st["trunk"][-1][0].out_features
-        ok = ok and layer(3, 0, k, -1, 0, actor.actor_d.out_features, 0, 0, actor.actor_d.weight, actor.actor_d.bias)
-        ok = ok and layer(3, 0, k, -1, 0, actor.actor_c.out_features, 0, 1, actor.actor_c.weight, actor.actor_c.bias)
-        if not ok or len(ops) > _capi.MLP_MAX_OPS or k > cls.BUF_COLS[3]:
-            return None
-        self = cls(ops, params, actor.actor_c.out_features, out_widths=[actor.actor_d.out_features, actor.actor_c.out_features] + ([1] if part == "all" else []))
-        self.packed_floats = woff[0]
-        return self
+        p.layer(3, 0, k, -1, 0, actor.actor_d.out_features, 0, actor.actor_d.weight, actor.actor_d.bias, out=(0, 0))
+        p.layer(3, 0, k, -1, 0, actor.actor_c.out_features, 0, actor.actor_c.weight, actor.actor_c.bias, out=(1, 0))
+        return cls(p, actor.actor_c.out_features, out_widths=[actor.actor_d.out_features, actor.actor_c.out_features] + ([1] if part == "all" else []))
 
     # ---------------------------------------------------------------- device side
     def _ptr_arrays(self):
-        """device pointers of every layer's (weight, bias); entries of `params` may be callables that build the tensor from the
-        module's parameters (the structured matrices of the history encoder) -- the results stay referenced in self._built"""
-        self._built = [tuple((t() if callable(t) else t) for t in p) if p else None for p in self.params]
-        w = (C.c_void_p * self.n_ops)(*[(p[0].data_ptr() if p else None) for p in self._built])
-        b = (C.c_void_p * self.n_ops)(*[(p[1].data_ptr() if p and p[1] is not None else None) for p in self._built])
-        return w, b
+        """pointers of every layer's (weight, bias), the structured matrices of the history encoder built from the module's parameters as they are now"""
+        return self._prog.ptr_arrays()
 
     def pack(self):
-        w, b = self._ptr_arrays()
-        dev = next(p[0] for p in self._built if p).device
-        if self.packed is None:
-            self.packed = torch.zeros(self.packed_floats, dtype=torch.float32, device=dev)
-        for p in self._built:
-            if p and not (p[0].is_cuda and p[0].is_contiguous() and p[0].dtype == torch.float32):
-                raise RuntimeError("PolicyChain: parameters must be contiguous fp32 ROCm tensors")
-        API.launch("mlp_pack", self.ops, self.n_ops, w, b, _ptr(self.packed), self.packed_floats, on=dev)
+        self._prog.bind()          # every time: update_dagger changes the parameters the structured matrices are built from
+        self._prog.pack()
+        self.packed = self._prog.packed
 
     def forward(self, obs):
         """-> one (N, width) tensor per global output of the chain (policy chains: action mean, value).  The tensors are
@@ -1714,9 +1631,8 @@ class PolicyChain:
         out = self._out.get(n)
         if out is None:
             bufs = [torch.zeros(n, w, device=obs.device) for w in self.out_widths]
-            k = len(bufs)
-            out = self._out[n] = (bufs, (C.c_void_p * k)(*[b.data_ptr() for b in bufs]), (C.c_int64 * k)(*self.out_widths))
-        API.launch("mlp_forward", _ptr(obs), obs.stride(0), n, obs.shape[1], self.ops, self.n_ops, _ptr(self.packed), out[1], out[2], len(out[0]), on=obs)
+            out = self._out[n] = (bufs, mlp_program.out_tables(bufs))
+        self._prog.launch(obs, obs.shape[1], tables=out[1])
         return tuple(out[0])
 
 

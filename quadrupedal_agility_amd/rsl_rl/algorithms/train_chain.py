@@ -20,8 +20,8 @@ import os
 import torch
 
 from quadrupedal_agility_amd import _capi
-from quadrupedal_agility_amd._capi import _ptr
 from quadrupedal_agility_amd.rsl_rl.algorithms import fused
+from quadrupedal_agility_amd.rsl_rl.algorithms.mlp_program import Packer, Program
 
 MAX_ROWS = int(os.environ.get("QA_TRAIN_CHAIN_MAX_ROWS", "8192"))      # measured (r6, profiles/r6_chain_steps.txt): 3,072-row steps 30 % faster, 6,144-row steps 17 % faster than the three-stream autograd step; 12,288 rows and up: slower
 ENABLED = os.environ.get("QA_TRAIN_CHAIN", "1") != "0"
@@ -30,97 +30,6 @@ DISC_ENABLED = os.environ.get("QA_DISC_TRAIN_CHAIN", "1") != "0"
 
 def _pad4(n):
     return (int(n) + 3) // 4 * 4
-
-
-class _Program:
-    """an op list + its packed weights (fused.PolicyChain's pack / launch halves, with explicit output tables)"""
-
-    def __init__(self, lib=None, prefix="qa_"):
-        self.ops, self.params, self.woff = [], [], 0
-        self.packed = None
-        self.api = _capi.Api(lib, prefix)          # injection point of the tests (another library exporting the same entry points under another prefix); the default is libqa_sim.so, and it is required
-
-    def _add(self, op, param):
-        self.ops.append(op); self.params.append(param)
-
-    def copy(self, src, scol, dst, dcol, n, save=None):
-        kw = dict(flags=_capi.MLP_F_SAVE, out_index=save[0], out_col=save[1]) if save else {}
-        self._add(_capi.QaMlpOp(kind=_capi.MLP_COPY, src_buf=src, src_col=scol, dst_buf=dst, dst_col=dcol, k=0, n=n, **kw), None)
-
-    def load(self, aux, dst, dcol, n, save=None):
-        """scratch buffer <- columns of a global tensor (aux = (output slot, first column))"""
-        kw = dict(flags=_capi.MLP_F_SAVE, out_index=save[0], out_col=save[1]) if save else {}
-        self._add(_capi.QaMlpOp(kind=_capi.MLP_LOAD, src_buf=0, src_col=0, dst_buf=dst, dst_col=dcol, k=0, n=n, aux_index=aux[0], aux_col=aux[1], **kw), None)
-
-    def grad(self, src, scol, dst, dcol, n, act=0, aux=None, add=False, save=None):
-        flags = (_capi.MLP_F_ADD if add else 0) | (_capi.MLP_F_SAVE if save else 0)
-        kw = dict(out_index=save[0], out_col=save[1]) if save else {}
-        if aux:
-            kw.update(aux_index=aux[0], aux_col=aux[1])
-        self._add(_capi.QaMlpOp(kind=_capi.MLP_GRAD, src_buf=src, src_col=scol, dst_buf=dst, dst_col=dcol, k=0, n=n, act=act, flags=flags, **kw), None)
-
-    def layer(self, src, scol, k, dst, dcol, n, act, weight, bias, out=None, save=None, aux=None, transposed=False):
-        """dst >= 0: into scratch buffer dst (and, with `save` = (output, column), to that global output too); dst = -1: to `out` = (output, column)"""
-        cols = _capi.MLP_BUF_COLS
-        assert dst != src and scol % 4 == 0 and scol + k <= cols[src] + 4 and (dst < 0 or dcol + n <= cols[dst]), (src, scol, k, dst, dcol, n)
-        nt, kb = (n + 15) // 16, fused.PolicyChain.k_blocks(k, n)
-        base = sum(16 * (c + 4) for c in cols[:src])
-        assert base + 15 * (cols[src] + 4) + scol + 16 * kb <= sum(16 * (c + 4) for c in cols), "padded k-blocks beyond the kernel's LDS"
-        w_off = self.woff; b_off = w_off + nt * kb * 256; self.woff = b_off + nt * 16
-        flags = (_capi.MLP_F_SAVE if (save and dst >= 0) else 0) | (_capi.MLP_F_TRANSPOSED if transposed else 0)
-        oi, oc = (out if dst < 0 else save) or (0, 0)
-        ai, acol = aux or (0, 0)
-        self._add(_capi.QaMlpOp(kind=_capi.MLP_LAYER, src_buf=src, src_col=scol, dst_buf=dst, dst_col=dcol, k=k, n=n, act=act, out_index=oi, flags=flags,
-                                w_off=w_off, b_off=b_off, out_col=oc, aux_index=ai, aux_col=acol), (weight, bias))
-
-    def finish(self):
-        assert len(self.ops) <= _capi.MLP_MAX_OPS, len(self.ops)
-        self.n_ops = len(self.ops)
-        self.c_ops = (_capi.QaMlpOp * self.n_ops)(*self.ops)
-        self.w_ptrs = (C.c_void_p * self.n_ops)(*[(p[0].data_ptr() if p else None) for p in self.params])
-        self.b_ptrs = (C.c_void_p * self.n_ops)(*[(p[1].data_ptr() if p and p[1] is not None else None) for p in self.params])
-        for p in self.params:
-            if p and not ((p[0].is_cuda or self.api.prefix != "qa_") and p[0].is_contiguous() and p[0].dtype == torch.float32):
-                raise RuntimeError("train chain: parameters must be contiguous fp32 ROCm tensors")
-        dev = next(p[0] for p in self.params if p).device
-        self.packed = torch.zeros(self.woff, dtype=torch.float32, device=dev)
-
-    def pack(self):
-        self.api.launch("mlp_pack", self.c_ops, self.n_ops, self.w_ptrs, self.b_ptrs, _ptr(self.packed), self.woff, on=self.packed)
-
-    def launch(self, x, x_cols, outs):
-        k = len(outs)
-        ptrs = (C.c_void_p * k)(*[o.data_ptr() for o in outs]); strides = (C.c_int64 * k)(*[o.stride(0) for o in outs])
-        self.api.launch("mlp_forward", _ptr(x), x.stride(0), x.shape[0], x_cols, self.c_ops, self.n_ops, _ptr(self.packed), ptrs, strides, k, on=x)
-
-
-class _Packer:
-    """qa_mlp_pack for SEVERAL programs in one launch: their layers as one op list over one packed buffer (each program's `packed` becomes its slice).
-    The weights change with every optimiser step, so a chain step repacks before it runs: one launch instead of one per program."""
-
-    def __init__(self, programs):
-        p0 = programs[0]
-        self.prog = p0
-        total = sum(p.woff for p in programs)
-        self.buf = torch.zeros(total, dtype=torch.float32, device=p0.packed.device)
-        ops, w, b, off = [], [], [], 0
-        for p in programs:
-            p.packed = self.buf[off:off + p.woff]
-            for op, param in zip(p.ops, p.params):
-                if op.kind == _capi.MLP_LAYER:
-                    o2 = _capi.QaMlpOp.from_buffer_copy(op)
-                    o2.w_off += off; o2.b_off += off
-                    ops.append(o2); w.append(param[0].data_ptr()); b.append(param[1].data_ptr() if param[1] is not None else None)
-            off += p.woff
-        assert off == total
-        M = _capi.MLP_MAX_OPS            # (a pack call takes at most this many layers: the task-level step's 30 go in two)
-        self.calls = [((_capi.QaMlpOp * len(ops[i:i + M]))(*ops[i:i + M]), len(ops[i:i + M]), (C.c_void_p * len(ops[i:i + M]))(*w[i:i + M]),
-                       (C.c_void_p * len(ops[i:i + M]))(*b[i:i + M])) for i in range(0, len(ops), M)]
-        self.total = total
-
-    def pack(self):
-        for ops, n, w, b in self.calls:
-            self.prog.api.launch("mlp_pack", ops, n, w, b, _ptr(self.buf), self.total, on=self.buf)
 
 
 class _Sides:
@@ -204,7 +113,7 @@ class PpoTrainChain:
         ain = t["ain"][0]
         # ---- forward program (what PolicyChain.describe builds for the rollout, plus the saves; the actor's explicit-state columns are the
         # OBSERVATION's: update_actor_critic feeds the true privileged state, only act() substitutes the estimate)
-        f = _Program(lib, prefix)
+        f = Program(lib, prefix)
         Z = 3
         f.copy(0, 0, Z, 0, lat_col, save=(T, ain))                                     # proprio + explicit
         f.copy(0, lat_col, 2, 0, n_lat)                                                # (a layer's source starts 16-byte aligned)
@@ -227,7 +136,7 @@ class PpoTrainChain:
         # ---- backward program.  Input tile = d loss / d action mean; the other three gradients are LOADED from their own tensors (the objectives'
         # kernels write them where they like).  outputs: 0 = gradient tape (written), 1 = activation tape, 2 = d value, 3 = d estimate, 4 = d latent (read)
         G, A, DV, DE, DP = 0, 1, 2, 3, 4
-        b = _Program(lib, prefix)
+        b = Program(lib, prefix)
         b.load((DV, 0), 1, 0, 1)
         b.layer(1, 0, 1, Z, 0, c_w[2], D, ac.critic_head.weight, None, save=(G, g["c3"][0]), aux=(A, t["c3"][0]), transposed=True)
         b.layer(Z, 0, c_w[2], 2, 0, c_w[1], D, c3.weight, None, save=(G, g["c2"][0]), aux=(A, t["c2"][0]), transposed=True)
@@ -244,7 +153,7 @@ class PpoTrainChain:
         b.layer(Z, 0, e_w[1], 2, 0, e_w[0], D, e2.weight, None, save=(G, g["e1"][0]), aux=(A, t["e1"][0]), transposed=True)
         b.finish()
         self.fwd, self.bwd = f, b
-        self._packer = _Packer([f, b])
+        self._packer = Packer([f, b])
         dev = a1.weight.device
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         self.tape, self.gtape = z(rows, self.tape_cols), z(rows, self.gtape_cols)
@@ -349,21 +258,21 @@ class DiscTrainChain:
         self.wh, self.bh_dummy = z(8, w2), None                  # the heads' weights stacked (refreshed per step: they change with every optimiser step)
         R = 2                                                    # ReLU
         DR = _capi.MLP_ACT_RELU_GRAD
-        f = _Program(lib, prefix)
+        f = Program(lib, prefix)
         f.layer(0, 0, k0, 1, 0, w1, R, l1.weight, l1.bias, save=(0, H1))
         f.layer(1, 0, w1, 2, 0, w2, R, l2.weight, l2.bias, save=(0, H2))
         f.layer(2, 0, w2, -1, 0, 1, 0, disc.linear.weight, disc.linear.bias, out=(1, 0))
         f.layer(2, 0, w2, -1, 0, 1, 0, disc.encoder_eps.weight, disc.encoder_eps.bias, out=(2, 0))
         f.layer(2, 0, w2, -1, 0, disc.classifier.out_features, 0, disc.classifier.weight, disc.classifier.bias, out=(3, 0))
         f.finish()
-        p = _Program(lib, prefix)                                # outputs: 0 = vu (written), 1 = the U rows of the activation tape (read), 2 = g
+        p = Program(lib, prefix)                                # outputs: 0 = vu (written), 1 = the U rows of the activation tape (read), 2 = g
         p.layer(0, 0, 1, 2, 0, w2, DR, disc.linear.weight, None, save=(0, V2), aux=(1, H2), transposed=True)
         p.layer(2, 0, w2, 1, 0, w1, DR, l2.weight, None, save=(0, V1), aux=(1, H1), transposed=True)
         p.layer(1, 0, w1, 2, 0, k0, 0, l1.weight, None, save=(2, 0), transposed=True)
         p.layer(2, 0, k0, 1, 0, w1, DR, l1.weight, None, save=(0, U1), aux=(1, H1))
         p.layer(1, 0, w1, -1, 0, w2, DR, l2.weight, None, out=(0, U2), aux=(1, H2))
         p.finish()
-        b = _Program(lib, prefix)   # input tile = d loss / d logit; outputs: 0 = gradient tape (written), 1 = activation tape, 2 = d eps, 3 = d class logits (read), 4 = the
+        b = Program(lib, prefix)   # input tile = d loss / d logit; outputs: 0 = gradient tape (written), 1 = activation tape, 2 = d eps, 3 = d class logits (read), 4 = the
                                     # three side by side as one (R, 8) matrix (written: the stacked heads' weight-gradient product reads it)
         b.copy(0, 0, 1, 0, 1, save=(4, 0))
         b.load((2, 0), 1, 1, 1, save=(4, 1))
@@ -372,7 +281,7 @@ class DiscTrainChain:
         b.layer(2, 0, w2, -1, 0, w1, DR, l2.weight, None, out=(0, GH1), aux=(1, H1), transposed=True)
         b.finish()
         self.fwd, self.pen, self.bwd = f, p, b
-        self._packer = _Packer([f, p, b])
+        self._packer = Packer([f, p, b])
         # opt-in side streams (QA_TRAIN_CHAIN_SIDES=1; measured slower): 3 = what `beside()` is handed.  (The three optimisers were once forked onto 1 / 2 as
         # well -- they share the trunk's parameters and must run one after the other: removed in r6.)
         self.sides = _Sides(dev, 4) if (SIDE_STREAMS and prefix == "qa_") else None
@@ -549,7 +458,7 @@ class TscTrainChain:
         T, LG, MU, VAL, EST, PRIV = 0, 1, 2, 3, 4, 5
         tin = t["tin"][0]
         c_lats, c_exp, c_lat = a, a + n_lats, a + n_lats + n_exp          # columns of the trunk's input row
-        f = _Program(lib, prefix)
+        f = Program(lib, prefix)
         # critic first: it may use every scratch buffer
         f.layer(0, 0, n_obs, 1, 0, cw[0], E, c1.weight, c1.bias, save=(T, t["c1"][0]))
         f.layer(1, 0, cw[0], 2, 0, cw[1], E, c2.weight, c2.bias, save=(T, t["c2"][0]))
@@ -581,7 +490,7 @@ class TscTrainChain:
         dev = t1.weight.device
         self.wh = torch.zeros(_pad4(nh), tw[2], dtype=torch.float32, device=dev)      # the two heads' weights stacked; refreshed by pack()
         nd = hd.out_features
-        b = _Program(lib, prefix)
+        b = Program(lib, prefix)
         b.copy(0, 0, 3, 0, nd, save=(GH, 0))
         b.load((DM, 0), 3, nd, hc.out_features, save=(GH, nd))
         b.layer(3, 0, _pad4(nh), 1, 0, tw[2], D, self.wh, None, save=(G, g["t3"][0]), aux=(A, t["t3"][0]), transposed=True)
@@ -603,7 +512,7 @@ class TscTrainChain:
         b.layer(2, 0, ew[1], 3, 0, ew[0], D, e2.weight, None, save=(G, g["e1"][0]), aux=(A, t["e1"][0]), transposed=True)
         b.finish()
         self.fwd, self.bwd = f, b
-        self._packer = _Packer([f, b])
+        self._packer = Packer([f, b])
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         self.tape, self.gtape, self.gh = z(rows, self.tape_cols), z(rows, self.gtape_cols), z(rows, _pad4(nh))
         self.logits, self.mean, self.value, self.est, self.priv = z(rows, nd), z(rows, hc.out_features), z(rows, 1), z(rows, n_exp), z(rows, n_lat)

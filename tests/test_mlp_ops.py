@@ -553,7 +553,7 @@ def test_every_shipped_training_program_is_accepted_and_the_packers_joint_list_i
     """the rule above is about ONE launch: each program the three training chains describe passes the library's own validation (qa_mlp_strands,
     host-only), while the op list their packer hands qa_mlp_pack -- the layers of a step's programs side by side, one program writing the tape slot
     the next one reads -- is no program to run: qa_mlp_pack must not apply the rule to it (it did once, and every chain step failed to pack)"""
-    from quadrupedal_agility_amd.rsl_rl.algorithms import train_chain
+    from quadrupedal_agility_amd.rsl_rl.algorithms import mlp_program, train_chain
     from tests.test_policy_chain import tsc_modules
     from tests.test_train_chain import _disc, _modules
     lib = load_oracle()
@@ -564,7 +564,7 @@ def test_every_shipped_training_program_is_accepted_and_the_packers_joint_list_i
     crossing = 0
     for chain in chains:
         assert chain is not None
-        for prog in [v for v in vars(chain).values() if isinstance(v, train_chain._Program)]:
+        for prog in [v for v in vars(chain).values() if isinstance(v, mlp_program.Program)]:
             ns, _ = _strands(qa(), "qa_", prog.c_ops, prog.n_ops)
             assert ns >= 1, qa().qa_last_error().decode()
             assert _strands(lib, "qo_", prog.c_ops, prog.n_ops)[0] == ns

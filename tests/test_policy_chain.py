@@ -93,6 +93,24 @@ def test_description_refuses_what_the_kernel_cannot_hold():
     np.testing.assert_allclose(mean, rm.numpy(), rtol=1e-4, atol=2e-5)
 
 
+@pytest.mark.parametrize("width,described", [(512, True), (528, False)])
+def test_description_holds_a_layer_to_the_kernels_32_column_tiles(width, described):
+    """a layer has at most 4 * MLP_WAVES = 32 column tiles of 16 (mlp_check, csrc/qa_policy.hip).  Scratch buffer 1 is 576 columns wide, so a first
+    hidden layer of 528 units (33 tiles) fits every buffer and is still no program: it must be declined here, not rejected by the library on the
+    fast path.  512 (32 tiles) and 528 are the two smallest widths on either side of the limit; the library's host-only validation
+    (qa_mlp_strands) and the oracle's take what is described."""
+    from tests.oracle_lib import load_oracle
+    ac, est, _ = modules(hidden=(width, 256, 128))
+    chain = PolicyChain.describe(ac, est, True)
+    assert (chain is not None) == described
+    if described:
+        qa, qo = _capi.load_library(), load_oracle()
+        strands = (C.c_int32 * chain.n_ops)()
+        ns = qa.qa_mlp_strands(chain.ops, chain.n_ops, 4, strands)
+        assert ns >= 1, qa.qa_last_error().decode()
+        assert qo.qo_mlp_strands(chain.ops, chain.n_ops, 4, (C.c_int32 * chain.n_ops)()) == ns
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [1, 16, 100, 4096])
 def test_hip_chain_matches_twin_and_torch(n):
