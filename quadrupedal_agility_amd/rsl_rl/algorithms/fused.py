@@ -885,6 +885,17 @@ def pair_losses_raw(jobs):
     return outs
 
 
+def latent_and_estimator_losses(priv_latent, hist_latent, est, target, coef):
+    """The two small regressions of either learner's PPO step: row L2 of the privileged latent against the history latent, gradient times `coef`, and
+    MSE of the estimator against its `target` columns -> (priv_reg_loss, g_priv), (est_loss, g_est).  ONE launch (ABI 18: both losses, their finishes
+    and the multiply; were five) if `coef` is an fp32 device scalar here (a recorded step's) and QA_PAIR_LOSSES is not 0; same arithmetic either way."""
+    if torch.is_tensor(coef) and coef.dtype == torch.float32 and coef.device == est.device and os.environ.get("QA_PAIR_LOSSES", "1") != "0":
+        return pair_losses_raw([(priv_latent, hist_latent, PAIR_ROW_L2, coef), (est, target, PAIR_MSE, None)])
+    priv_reg_loss, g_priv = pair_loss_raw(priv_latent, hist_latent, PAIR_ROW_L2)
+    g_priv = g_priv * coef
+    return (priv_reg_loss, g_priv), pair_loss_raw(est, target, PAIR_MSE)
+
+
 def accumulate_scalars(acc, scalars):
     """acc[i] += scalars[i] (0-d / 1-element fp32 ROCm tensors, possibly views of different kernels' outputs) in ONE launch (qa_accumulate_scalars) instead of
     torch.stack + add_; falls back to those for anything else"""

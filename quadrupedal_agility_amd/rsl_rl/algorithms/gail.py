@@ -328,19 +328,15 @@ class SSInfoGAIL:
     def _ac_updates_recorded(self, perm=None):
         """The 20 PPO minibatch steps of an iteration are ~270 launches each and the host cannot issue them faster than
         the GPU retires them (the iteration time followed the host's launch rate, 59-78 ms, not the GPU's 57 ms of kernel
-        time).  One step -- minibatch gather from a device index buffer, both forwards, the fused objective, both
-        backward passes, clipping, the KL-adaptive learning rate and the Adam updates -- is recorded into a hipGraph once
-        and replayed; per step the host only copies the next 24,576 indices into the index buffer.
-        Data-parallel runs record the step as TWO graphs around the gradient collective, which stays an ordinary
-        launch: [gather .. backward, gradients + KL packed into a persistent bucket] -> all-reduce(bucket) ->
-        [scale + unpack, clip, LR rule, Adam]."""
+        time).  One step -- both forwards, the fused objective, both backward passes, clipping, the KL-adaptive learning
+        rate and the Adam updates -- is recorded into a hipGraph once and replayed; feeding (permuted slots), the forms of a
+        recording (data-parallel: TWO graphs around the gradient collective) and the replays are recording.MinibatchSchedule."""
         dev, st = self.device, self.storage
         batch = st.num_envs * st.num_transitions_per_env
         mb = batch // self.num_mini_batches
         nmb = self.num_mini_batches
         if self._ac_graph is None:
             try:
-                self._acc_ac = torch.zeros(6, device=dev)
                 self._priv_coef_dev = torch.zeros((), device=dev)
                 flat = [x.flatten(0, 1) for x in (st.observations, st.actions, st.values, st.advantages, st.returns,
                                                   st.actions_log_prob, st.mu, st.sigma)]
@@ -349,57 +345,33 @@ class SSInfoGAIL:
                 if (fused_mod.pad_k() or self._train_chain_rows(mb) is not None) and getattr(st, "_obs_padded", None) is not None:
                     flat[0] = st._obs_padded.flatten(0, 1)      # the minibatch copy keeps the zero padding (672 columns): 16-byte aligned GEMM rows
                 sync = self.grad_sync
-                all_params = list(self.estimator.parameters()) + list(self.actor_critic.parameters())
-
                 # The history encoder is not trained by these steps (its latent enters the regulariser detached; its own
                 # regression is update_dagger), so its output for a sample is the same in all 5 epochs: evaluate it ONCE per
                 # update for the whole rollout (~0.6 ms) instead of once per minibatch step (20 x 0.16 ms) and gather rows.
-                self._hist_latent_all = torch.zeros(batch, self.num_latent, device=dev)
+                hist_latent_all = torch.zeros(batch, self.num_latent, device=dev)
                 self._hist_cols = slice(self.num_prop + self.num_explicit + self.num_latent,
                                         self.num_prop + self.num_explicit + self.num_latent + self.num_hist * self.num_prop)
-                # The reference draws ONE permutation per update and reuses its 4 slices in all 5 epochs (rollout_storage.py:122-157): the
-                # rollout is gathered into permuted order ONCE per update (one qa_gather_rows launch over all 98,304 rows, 0.17 ms) and
-                # minibatch i is rows [i mb, (i+1) mb) of that copy -- a recorded step per minibatch slot (they share one memory pool and never
-                # run concurrently) instead of a 43 us gather at the head of each of the 20 steps (r3: -0.7 ms per iteration).
-                self._gather_srcs = flat + [self._hist_latent_all]
-                self._perm_bufs = [torch.empty(nmb * mb, x.shape[1] if x.dim() == 2 else 1, device=dev) for x in self._gather_srcs]
+                # The reference draws ONE permutation per update and reuses its 4 slices in all 5 epochs (rollout_storage.py:122-157): permuted slots, one
+                # gather over all 98,304 rows per update (0.17 ms) instead of a 43 us gather at the head of each of the 20 steps (r3: -0.7 ms per iteration)
+                sched = recording.MinibatchSchedule(nmb, mb, flat + [hist_latent_all], permuted=True)
 
-                def front(i):
-                    obs, act, val, adv, ret, logp, mu, sig, hl = (b[i * mb:(i + 1) * mb] for b in self._perm_bufs)
-                    return self._ac_forward_backward((obs, obs, act, val, adv, ret, logp, mu, sig, (None, None), None, hl))
+                def front(obs, act, val, adv, ret, logp, mu, sig, hl):
+                    return self._ac_forward_backward((obs, obs, act, val, adv, ret, logp, mu, sig, (None, None), None, hl))[::-1]
+
+                def zero_grads():
+                    for o in (self.optim_ac, self.optim_estimator):
+                        o.zero_grad(set_to_none=True)
 
                 torch.cuda.synchronize()
-                for o in (self.optim_ac, self.optim_estimator):
-                    o.zero_grad(set_to_none=True)
+                zero_grads()
                 self._recording_ac = True
-                graphs = []
-                pool = torch.cuda.graph_pool_handle()
                 try:
                     # r6: steps that run as chain launches are short (~0.37 ms), and two consecutive replays are ~8.5 us apart on the device: the
                     # nmb slots of an epoch as ONE recording (one replay per epoch)
                     epoch_graph = sync is None and self._train_chain_rows(mb) is not None and os.environ.get("QA_STEP_UNROLL", "1") != "0"
-
-                    def slot(i):
-                        stats, kl = front(i)
-                        self._ac_apply(kl)
-                        fused_mod.accumulate_scalars(self._acc_ac, stats)       # (one launch; was torch.stack + add_)
-
-                    def epoch():
-                        for i in range(nmb):
-                            slot(i)
-                            for o in (self.optim_ac, self.optim_estimator):
-                                o.zero_grad(set_to_none=True)
-
-                    if epoch_graph:
-                        graphs.append((recording.record(epoch, pool=pool)[0], None, None))
-                    for i in range(0 if epoch_graph else nmb):
-                        if sync is None:
-                            graphs.append((recording.record(lambda: slot(i), pool=pool)[0], None, None))
-                        else:
-                            graphs.append(recording.record_data_parallel(lambda: front(i)[::-1], self._ac_apply, self._acc_ac, all_params, sync.world, pool))
-                        for o in (self.optim_ac, self.optim_estimator):       # the next slot's recording creates its gradients afresh
-                            o.zero_grad(set_to_none=True)
-                    self._ac_graph = graphs
+                    sched.record_steps(front, self._ac_apply, torch.zeros(6, device=dev), zero_grads, epoch=epoch_graph, sync=sync,
+                                       params=list(self.estimator.parameters()) + list(self.actor_critic.parameters()))
+                    self._ac_graph = sched
                 finally:
                     self._recording_ac = False
             except Exception as e:
@@ -409,17 +381,15 @@ class SSInfoGAIL:
                 for sample in st.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
                     acc += torch.stack(self.update_actor_critic(sample))
                 return acc
+        sched = self._ac_graph
         self._priv_coef_dev.fill_(float(self._priv_reg_coef_now()))
-        self._acc_ac.zero_()
+        sched.acc.zero_()
         with torch.no_grad():
-            self._hist_latent_all.copy_(self.actor_critic.infer_hist_latent(st.observations.flatten(0, 1)[:, self._hist_cols]))
+            sched.srcs[-1].copy_(self.actor_critic.infer_hist_latent(st.observations.flatten(0, 1)[:, self._hist_cols]))
         if perm is None:
             perm = torch.randperm(nmb * mb, device=dev)   # one permutation for all epochs (rollout_storage.py:122-157)
-        fused_mod.gather_rows(perm, self._gather_srcs, dsts=self._perm_bufs)
-        for _ in range(self.num_learning_epochs):
-            for ga, gb, bucket in self._ac_graph:            # nmb recordings of one step each, or one of the whole epoch
-                recording.replay_step(ga, gb, bucket, self.grad_sync)
-        return self._acc_ac.clone()
+        sched.run(perm, self.num_learning_epochs, self.grad_sync)
+        return sched.acc.clone()
 
     def _disc_updates_recorded(self, n_steps, mb, tables=None):
         """The discriminator steps are tiny (3 x 1228 x 98 inputs, ~300 launches each, double backward) and therefore
@@ -631,14 +601,8 @@ class SSInfoGAIL:
                 with torch.no_grad():
                     hist_latent = ac.infer_hist_latent(obs[:, c:d])
             est = self.estimator(obs[:, :a])
-            if torch.is_tensor(priv_reg_coef) and priv_reg_coef.dtype == torch.float32 and priv_reg_coef.device == obs.device and os.environ.get("QA_PAIR_LOSSES", "1") != "0":
-                # r6 (ABI 18): one launch, rows through LDS (qa_pair_loss walks 24,576 rows of 29 floats lane by lane: 29 us each)
-                (priv_reg_loss, g_priv), (estimator_loss, g_est) = fused_mod.pair_losses_raw(
-                    [(priv_latent, hist_latent, fused_mod.PAIR_ROW_L2, priv_reg_coef), (est, obs[:, a:b], fused_mod.PAIR_MSE, None)])
-            else:
-                priv_reg_loss, g_priv = fused_mod.pair_loss_raw(priv_latent, hist_latent, fused_mod.PAIR_ROW_L2)
-                g_priv = g_priv * priv_reg_coef
-                estimator_loss, g_est = fused_mod.pair_loss_raw(est, obs[:, a:b], fused_mod.PAIR_MSE)
+            # (one launch, rows through LDS: qa_pair_loss walks 24,576 rows of 29 floats lane by lane, 29 us each)
+            (priv_reg_loss, g_priv), (estimator_loss, g_est) = fused_mod.latent_and_estimator_losses(priv_latent, hist_latent, est, obs[:, a:b], priv_reg_coef)
         mu = ac._actor_mean(obs.detach(), False)
         if self.branch_streams:
             cur.wait_stream(s_critic)
@@ -707,14 +671,7 @@ class SSInfoGAIL:
         if hist_latent is None:
             with torch.no_grad():
                 hist_latent = ac.infer_hist_latent(obs[:, c:d])
-        if torch.is_tensor(priv_reg_coef) and priv_reg_coef.dtype == torch.float32 and priv_reg_coef.device == obs.device and os.environ.get("QA_PAIR_LOSSES", "1") != "0":
-            # r6 (ABI 18): both losses, their finishes and the coefficient's multiply in ONE launch (were five)
-            (priv_reg_loss, g_priv), (estimator_loss, g_est) = fused_mod.pair_losses_raw(
-                [(priv_latent, hist_latent, fused_mod.PAIR_ROW_L2, priv_reg_coef), (est, obs[:, a:b], fused_mod.PAIR_MSE, None)])
-        else:
-            priv_reg_loss, g_priv = fused_mod.pair_loss_raw(priv_latent, hist_latent, fused_mod.PAIR_ROW_L2)
-            g_priv = g_priv * priv_reg_coef
-            estimator_loss, g_est = fused_mod.pair_loss_raw(est, obs[:, a:b], fused_mod.PAIR_MSE)
+        (priv_reg_loss, g_priv), (estimator_loss, g_est) = fused_mod.latent_and_estimator_losses(priv_latent, hist_latent, est, obs[:, a:b], priv_reg_coef)
         out, dmu, dstd, dvalue = fused_mod.ppo_loss_raw(mu, ac.std, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
                                                         clip=self.clip_param, c_surr=self.surrogate_loss_coef, c_value=self.value_loss_coef,
                                                         c_bound=self.bounds_loss_coef, c_entropy=self.entropy_coef,
@@ -1036,35 +993,31 @@ class SSInfoGAIL:
         n = self.num_learning_epochs * self.num_mini_batches
         st = self.storage
         if (self._on_gpu and self.use_update_graph and self.grad_sync is None and self._dagger_warm >= 1 and self._dagger_graph is not False):
-            # same recording scheme as the PPO step: gather from the device index buffer + one optimiser step per replay
+            # recording.MinibatchSchedule, index buffer: gather from the device index buffer + one optimiser step per replay
             mb = st.num_envs * st.num_transitions_per_env // self.num_mini_batches
             if self._dagger_graph is None:
                 try:
-                    self._dg_idx = torch.zeros(mb, dtype=torch.int64, device=self.device)
-                    self._dg_acc = torch.zeros((), device=self.device)
                     flat_obs = st.observations.flatten(0, 1)
-
-                    def one_step():
-                        self._dg_acc.add_(self._dagger_step(flat_obs[self._dg_idx]))
+                    sched = recording.MinibatchSchedule(self.num_mini_batches, mb, [flat_obs], permuted=False)
                     torch.cuda.synchronize()
                     self.optim_hist_encoder.zero_grad(set_to_none=True)
-                    self._dagger_graph, _ = recording.record(one_step)
+                    # (the whole step, optimiser included, is `_dagger_step`: nothing to apply between it and the accumulator)
+                    sched.record_steps(lambda idx: (None, self._dagger_step(flat_obs[idx])), lambda kl: None, torch.zeros((), device=self.device))
+                    self._dagger_graph = sched
                 except Exception as e:
                     recording.capture_failed("dagger update graph", e)
                     self._dagger_graph = False
             if self._dagger_graph:
-                self._dg_acc.zero_()
+                sched = self._dagger_graph
+                sched.acc.zero_()
                 if perm is None:
                     perm = torch.randperm(self.num_mini_batches * mb, device=self.device)
-                for _ in range(self.num_learning_epochs):
-                    for i in range(self.num_mini_batches):
-                        self._dg_idx.copy_(perm[i * mb:(i + 1) * mb])
-                        self._dagger_graph.replay()
+                sched.run(perm, self.num_learning_epochs)
                 self._dagger_calls += 1
                 self._dagger_warm += 1
                 st.clear()
                 self.priv_reg_counter += 1
-                return float(self._dg_acc) / n
+                return float(sched.acc) / n
         total = torch.zeros((), device=self.device)
         for sample in st.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, perm=perm):
             total += self._dagger_step(sample[0])

@@ -264,7 +264,7 @@ class PPO:
                 if self.desired_kl is not None and self.schedule == "adaptive":
                     self._adapt_from_kl(kl)
                 self._step_ac.step()
-                self._add_stats(sums, stats)
+                recording.accumulate(sums, stats)
                 continue
             ac.act(obs, hist_encoding=False)
             logp_d = ac.get_actions_log_prob_d(actions[:, 0])
@@ -361,19 +361,12 @@ class PPO:
                                             clip=self.clip_param, c_value=self.value_loss_coef, c_entropy=self.entropy_coef,
                                             clipped_value=self.use_clipped_value_loss)
             out, dlogits, dmean, dstd, dvalue = res
-            if torch.is_tensor(coef) and coef.dtype == torch.float32 and coef.device == obs.device and os.environ.get("QA_PAIR_LOSSES", "1") != "0":
-                # r6 (ABI 18): both losses, their finishes and the coefficient's multiply in ONE launch (were five); same arithmetic
-                (priv_reg_loss, g_priv), (est_loss, g_est) = fused.pair_losses_raw(
-                    [(priv_latent, hist_latent, fused.PAIR_ROW_L2, coef), (est, obs[:, self._priv_slice(True)], fused.PAIR_MSE, None)])
-            else:
-                priv_reg_loss, g_priv = fused.pair_loss_raw(priv_latent, hist_latent, fused.PAIR_ROW_L2)
-                est_loss, g_est = fused.pair_loss_raw(est, obs[:, self._priv_slice(True)], fused.PAIR_MSE)
-                g_priv = g_priv * coef
+            (priv_reg_loss, g_priv), (est_loss, g_est) = fused.latent_and_estimator_losses(priv_latent, hist_latent, est, obs[:, self._priv_slice(True)], coef)
             chain.backward(g_est, dlogits, dmean, dvalue, g_priv)
             if self.grad_sync is not None:
                 fused.flush_pending_grads()
             ac.std.grad = dstd.view_as(ac.std)
-            return out[4], (out[2], out[1], est_loss, priv_reg_loss)       # (a tuple: `_add_stats` puts them on the accumulator in one launch)
+            return out[4], (out[2], out[1], est_loss, priv_reg_loss)       # (a tuple: `recording.accumulate` puts them on the accumulator in one launch)
         if self.use_fused_loss and obs.is_cuda and fused.ENABLED and isinstance(ac.std, nn.Parameter):
             from quadrupedal_agility_amd.rsl_rl.modules.actor_critic import _head
             emb = ac.actor(obs, False)
@@ -396,14 +389,6 @@ class PPO:
         loss.backward()
         return kl, torch.stack(stats)
 
-    @staticmethod
-    def _add_stats(acc, stats):
-        """the step's four logged values onto the accumulator: a stacked tensor (autograd path), or four device scalars (chain path: one launch)"""
-        if torch.is_tensor(stats):
-            acc.add_(stats)
-        else:
-            fused.accumulate_scalars(acc, list(stats))
-
     def _train_chain(self, obs, cobs):
         """train_chain.TscTrainChain for this minibatch size, or None (many rows, the critic on another row than the actor, head widths the fused
         objective was not built for, networks that are not the reference's Linear / ELU / tanh stacks)"""
@@ -423,59 +408,48 @@ class PPO:
         """The 20 minibatch steps of update() as replays of recorded launches (hipGraph).  One step -- nine indexed reads of the
         rollout, estimator / actor / critic forward, the two clipped surrogates, both backward passes, clipping, the KL-adaptive
         learning rate (on the device) and the two Adam steps -- is ~400 launches of mostly small kernels: at the 1024 envs per GPU of
-        BASELINE's 8-GPU teacher job the host cannot issue them as fast as the GPU retires them.  Per step the host copies the next
-        index slice and replays.  The privileged-latent regulariser's target (history encoder, not trained by these steps) is evaluated
-        once per update for the whole rollout.  Data-parallel runs record the step as TWO graphs around the gradient collective:
-        [gather .. both backward passes, gradients + KL packed into a persistent bucket] -> all-reduce(bucket) -> [unpack, LR rule,
-        both Adam steps].  Returns the summed losses, or None when capture is not possible (the caller stays eager)."""
+        BASELINE's 8-GPU teacher job the host cannot issue them as fast as the GPU retires them.  The privileged-latent regulariser's
+        target (history encoder, not trained by these steps) is evaluated once per update for the whole rollout.  Feeding, the forms of a
+        recording and the replay loop are recording.MinibatchSchedule; data-parallel runs record the step as TWO graphs around the gradient
+        collective (recording.record_data_parallel).  Returns the summed losses, or None when capture is not possible (the caller stays eager)."""
         dev, st, ac = self.device, self.storage, self.actor_critic
         batch = st.num_envs * st.num_transitions_per_env
-        mb = batch // self.num_mini_batches
+        nmb = self.num_mini_batches
+        mb = batch // nmb
         flat = [x.flatten(0, 1) for x in (st.observations, st.actions, st.values, st.advantages, st.returns, st.actions_log_prob_d,
                                           st.actions_log_prob_c, st.mu, st.sigma)]
         if self._graph is None:
             try:
-                self._mb_idx = torch.zeros(mb, dtype=torch.int64, device=dev)
-                self._acc = torch.zeros(4, device=dev)
                 self._coef_dev = torch.zeros((), device=dev)
-                self._hist_latent_all = torch.zeros(batch, ac.actor.infer_hist_latent(flat[0][:2]).shape[1], device=dev)
+                hist_latent_all = torch.zeros(batch, ac.actor.infer_hist_latent(flat[0][:2]).shape[1], device=dev)
                 self._lr_dev = torch.full((), float(self._learning_rate), dtype=torch.float32, device=dev)
                 for g in self.optimizer.param_groups:
                     g["lr"] = self._lr_dev
                 sync = self.grad_sync
-                params = list(self.estimator.parameters()) + list(ac.parameters())
-
                 cflat = st.privileged_observations.flatten(0, 1) if st.privileged_observations is not None else None
+                srcs = flat + [hist_latent_all] + ([cflat] if cflat is not None else [])
+                # r6: on one GPU, with steps that run as chain launches (<= 8192 rows, ~0.65 ms each), the schedule feeds permuted slots and the slots of an
+                # epoch are ONE recording -- 5 replays per update instead of 20 x (index copy, replay, gather); otherwise the index buffer, the step as one
+                # graph or as the data-parallel pair
+                permuted = (sync is None and cflat is None and os.environ.get("QA_STEP_UNROLL", "1") != "0"
+                            and self._train_chain(flat[0][:mb], flat[0][:mb]) is not None)
+                sched = recording.MinibatchSchedule(nmb, mb, srcs, permuted)
+                if permuted:
+                    sched.fill(torch.arange(nmb * mb, device=dev))          # the warm-up pass below runs slot 0 for real
 
-                def front():
-                    srcs = flat + [self._hist_latent_all] + ([cflat] if cflat is not None else [])
-                    got = fused.gather_rows(self._mb_idx, srcs)          # the indexed reads of a minibatch in ONE launch
+                def front(*feed):
+                    got = feed if permuted else fused.gather_rows(feed[0], srcs)          # the indexed reads of a minibatch in ONE launch
                     rows, hl = list(got[:len(flat)]), got[len(flat)]
                     rows.insert(1, got[-1] if cflat is not None else rows[0])
                     return self._minibatch_forward_backward(rows, hl, self._coef_dev)
 
-                # r6: on one GPU, with steps that run as chain launches (<= 8192 rows, ~0.65 ms each), the rollout is gathered into permuted order ONCE per
-                # update (the reference draws one permutation for all epochs, :122-170) and minibatch i is rows [i mb, (i + 1) mb) of that copy; the slots of an
-                # epoch are ONE recording -- 5 replays per update instead of 20 x (index copy, replay, gather).  The behaviour-level learner's scheme since r3.
-                nmb = self.num_mini_batches
-                self._epoch_graph, self._bucket = False, None
-                if sync is None and cflat is None and os.environ.get("QA_STEP_UNROLL", "1") != "0":
-                    srcs_all = flat + [self._hist_latent_all]
-                    bufs = fused.gather_rows(torch.arange(nmb * mb, device=dev), srcs_all)          # (also fills the buffers for the warm-up pass below)
-                    if self._train_chain(bufs[0][:mb], bufs[0][:mb]) is not None:
-                        self._perm_bufs, self._gather_srcs, self._epoch_graph = bufs, srcs_all, True
-
-                def front_slot(i):
-                    rows = [b[i * mb:(i + 1) * mb] for b in self._perm_bufs[:len(flat)]]
-                    hl = self._perm_bufs[len(flat)][i * mb:(i + 1) * mb]
-                    rows.insert(1, rows[0])
-                    return self._minibatch_forward_backward(rows, hl, self._coef_dev)
-
-                # (an attribute: its merged device tables are read by every REPLAY -- as a local of this capture block they were freed when it
+                # (held by the schedule: its merged device tables are read by every REPLAY -- as a local of this capture block they were freed when it
                 # returned, and the replays faulted)
-                pair = self._step_pair = fused.ClipAdamPair(self._step_estimator, self._step_ac) if os.environ.get("QA_ADAM_PAIR", "1") != "0" else None
+                pair = fused.ClipAdamPair(self._step_estimator, self._step_ac) if os.environ.get("QA_ADAM_PAIR", "1") != "0" else None
+                sched.held.append(pair)
 
                 def apply(kl):
+                    kl = kl.reshape(())
                     # r6 (ABI 18): the two clipped Adam steps and the KL rule between them as three launches (same kernels, same sums: bit-identical)
                     if pair is not None and kl.dtype == torch.float32 and pair.step(kl, self.desired_kl):
                         return
@@ -484,6 +458,9 @@ class PPO:
                     self._step_estimator.step()
                     fused.kl_lr_rule(kl, self.desired_kl, self._lr_dev)
                     self._step_ac.step()
+
+                def zero_grads():
+                    self.optimizer.zero_grad(set_to_none=True); self.estimator_optimizer.zero_grad(set_to_none=True)
 
                 # autograd keeps one AccumulateGrad node per parameter, tied to the stream it was first used on and alive as long as
                 # any graph references it: drop what the eager update left (the modules' distribution objects hold a graph), then run
@@ -495,36 +472,18 @@ class PPO:
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
-                    self.optimizer.zero_grad(set_to_none=True); self.estimator_optimizer.zero_grad(set_to_none=True)
-                    front_slot(0) if self._epoch_graph else front()
+                    zero_grads()
+                    front(*sched.feeds()[0])
                 torch.cuda.current_stream().wait_stream(side)
                 torch.cuda.synchronize()
                 if pair is not None:
                     pair.warm()                 # the merged optimiser tables, built OUTSIDE the capture (the gradients of the pass above exist)
                 ac.distribution_d = ac.distribution_c = None
                 gc.collect()
-                self.optimizer.zero_grad(set_to_none=True); self.estimator_optimizer.zero_grad(set_to_none=True)
-
-                def step(fwd_bwd, *slot):
-                    kl, stats = fwd_bwd(*slot)
-                    apply(kl.reshape(()))
-                    self._add_stats(self._acc, stats)
-
-                def epoch():
-                    for i in range(nmb):
-                        step(front_slot, i)
-                        self.optimizer.zero_grad(set_to_none=True); self.estimator_optimizer.zero_grad(set_to_none=True)
-
-                def front_stacked():          # the statistics as ONE tensor, an attribute like the bucket: both are read by every replay of the second graph
-                    kl, st_ = front()
-                    self._stats_tmp = st_ if torch.is_tensor(st_) else torch.stack(list(st_))
-                    return kl, self._stats_tmp
-
-                if self._epoch_graph or sync is None:
-                    self._graph = (recording.record(epoch if self._epoch_graph else lambda: step(front))[0], None)
-                else:
-                    ga, gb, self._bucket = recording.record_data_parallel(front_stacked, apply, self._acc, params, sync.world, torch.cuda.graph_pool_handle())
-                    self._graph = (ga, gb)
+                zero_grads()
+                sched.record_steps(front, apply, torch.zeros(4, device=dev), zero_grads, epoch=permuted, sync=sync,
+                                   params=list(self.estimator.parameters()) + list(ac.parameters()))
+                self._graph = (*sched[0][:2], sched)          # (ga, gb, and through the schedule everything their replays read)
                 # the capture ran no kernels: parameters, Adam moments and the LR are untouched; the replays below do this update
             except Exception as e:
                 recording.capture_failed("tsc ppo update graph", e)
@@ -535,22 +494,14 @@ class PPO:
                     for g in self.optimizer.param_groups:
                         g["lr"] = lr
                 return None
+        sched = self._graph[2]
         self._coef_dev.fill_(float(coef))
-        self._acc.zero_()
+        sched.acc.zero_()
         with torch.no_grad():
-            self._hist_latent_all.copy_(ac.actor.infer_hist_latent(flat[0]))
-        ga, gb = self._graph
-        perm = torch.randperm(self.num_mini_batches * mb, device=dev)          # one permutation for all epochs (:122-170)
-        if getattr(self, "_epoch_graph", False):
-            fused.gather_rows(perm, self._gather_srcs, dsts=self._perm_bufs)
-            for _ in range(self.num_learning_epochs):
-                ga.replay()
-            return self._acc.clone()
-        for _ in range(self.num_learning_epochs):
-            for i in range(self.num_mini_batches):
-                self._mb_idx.copy_(perm[i * mb:(i + 1) * mb])
-                recording.replay_step(ga, gb, self._bucket, self.grad_sync)
-        return self._acc.clone()
+            sched.srcs[len(flat)].copy_(ac.actor.infer_hist_latent(flat[0]))
+        perm = torch.randperm(nmb * mb, device=dev)          # one permutation for all epochs (:122-170)
+        sched.run(perm, self.num_learning_epochs, self.grad_sync)
+        return sched.acc.clone()
 
     def _dagger_step(self, obs):
         """one minibatch of the history-encoder regression (:264-283): || priv_encoder(latent) - history_encoder(history) ||_2 row mean, one Adam step"""
@@ -573,7 +524,7 @@ class PPO:
 
     def update_dagger(self):
         """History-encoder regression onto the privileged latent every dagger_update_freq iterations (:264-283).  r6: on one GPU the 20 steps are
-        replays of ONE recorded step (the same scheme as the behaviour-level learner's, rsl_rl/algorithms/gail.py `update_dagger`): eager they
+        replays of ONE recorded step (recording.MinibatchSchedule, index buffer, as the behaviour-level learner's `update_dagger`): eager they
         are ~1.6 ms each of launch-bound small kernels, and the iteration that carries them took 57 ms against 24 (1024 envs)."""
         ac, st = self.actor_critic, self.storage
         n = self.num_learning_epochs * self.num_mini_batches
@@ -584,25 +535,23 @@ class PPO:
                 and torch.device(self.device).type == "cuda"):
             if self._dagger_graph is None:
                 try:
-                    self._dg_idx = torch.zeros(mb, dtype=torch.int64, device=self.device)
-                    self._dg_acc = torch.zeros((), device=self.device)
-                    self._dg_rows = (obs_all.data_ptr(), mb)
+                    sched = recording.MinibatchSchedule(self.num_mini_batches, mb, [obs_all], permuted=False)
                     torch.cuda.synchronize()
                     self.hist_encoder_optimizer.zero_grad(set_to_none=True)
-                    self._dagger_graph, _ = recording.record(lambda: self._dg_acc.add_(self._dagger_step(obs_all[self._dg_idx])))
+                    # (the whole step, optimiser included, is `_dagger_step`: nothing to apply between it and the accumulator)
+                    sched.record_steps(lambda idx: (None, self._dagger_step(obs_all[idx])), lambda kl: None, torch.zeros((), device=self.device))
+                    self._dagger_graph = sched
                 except Exception as e:
                     recording.capture_failed("tsc dagger update graph", e)
                     self._dagger_graph = False
-            if self._dagger_graph and self._dg_rows == (obs_all.data_ptr(), mb):
-                self._dg_acc.zero_()
-                for _ in range(self.num_learning_epochs):
-                    for i in range(self.num_mini_batches):
-                        self._dg_idx.copy_(perm[i * mb:(i + 1) * mb])
-                        self._dagger_graph.replay()
+            sched = self._dagger_graph
+            if sched and (sched.srcs[0].data_ptr(), sched.mb) == (obs_all.data_ptr(), mb):          # (a storage built anew since the recording: eager)
+                sched.acc.zero_()
+                sched.run(perm, self.num_learning_epochs)
                 self._dagger_warm += 1
                 st.clear()
                 self.update_counter()
-                return float(self._dg_acc) / n
+                return float(sched.acc) / n
         total = torch.zeros((), device=self.device)
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
