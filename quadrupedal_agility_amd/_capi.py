@@ -82,7 +82,11 @@ TSC_EXTRA_POINTERS = _field_names(QaTscExtraRewards, only=C.c_void_p)
 
 _HOST_ONLY = ("last_error", "abi_version")              # no oracle twin and no status to check: load_library sets their restype itself
 ABI_SYMBOLS = [name for header, name, _, _ in H.prototypes if header == "qa_sim.h"]
-EXTENSION_SYMBOLS = [name for header, name, _, _ in H.prototypes if header != "qa_sim.h"]
+# tests/golden/abi.json records the two lists, the Structure classes and the public constants of this module.  The headers named here have a
+# record of their own beside it ({header: (record under tests/golden/, the header's structs)}; tools/abi_dump.py writes and checks both):
+# their entry points are bound like every other (bind_extensions goes by the headers), their structs are read by the module that uses them.
+_RECORDED_APART = {"qa_tsc_scan_obstacles.h": ("abi_scan_obstacles.json", ("qa_tsc_scan_obstacles",))}
+EXTENSION_SYMBOLS = [name for header, name, _, _ in H.prototypes if header != "qa_sim.h" and header not in _RECORDED_APART]
 
 
 def _bind(lib, prefix, extension):
@@ -100,8 +104,8 @@ def bind(lib, prefix):
 
 
 def bind_extensions(lib, prefix="qa_"):
-    """Entry points declared in the extension headers next to include/qa_sim.h (EXTENSION_SYMBOLS): exported by the HIP library only,
-    no oracle twin, not part of ABI_SYMBOLS."""
+    """Entry points declared in the extension headers next to include/qa_sim.h (EXTENSION_SYMBOLS and those of _RECORDED_APART): exported by
+    the HIP library only, no oracle twin, not part of ABI_SYMBOLS."""
     return _bind(lib, prefix, True)
 
 

@@ -8,6 +8,8 @@
 #include <stdio.h>
 
 #include "../../include/qa_sim.h"
+#include "../../include/qa_tsc_scan_obstacles.h"
+#include "qa_obst_surface.h"
 #include "qa_tsc_rewards.h"
 
 extern thread_local char qa_err_buf[512];
@@ -525,6 +527,83 @@ __global__ void __launch_bounds__(64 * OBS_WAVES) qa_tsc_observations_kernel(qa_
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// qa_tsc_observations_obstacles' second launch (include/qa_tsc_scan_obstacles.h): behind qa_tsc_observations_kernel on the same stream, it
+// measures again, on the obstacles' rendered surface (qa_obst_surface.h), the scan points that lie inside a footprint, and rewrites what
+// such a point determines -- its measured height, its entry of the 800 row and, for point 67, the three root-height entries.  It stores
+// nothing else, so everything a record does not cover stays the static launch's bit for bit; an overlay and not a second instantiation of
+// the kernel above, because two compilations of one source need not round alike.
+// The static kernel's layout: one wavefront per env, 4 envs per workgroup, 3 scan points per lane, addresses clamped, stores predicated,
+// a ragged tail that stores nothing; load-first, and the point's world position is that kernel's expression (this file is compiled
+// without contraction, so it is that kernel's value).  Most envs stand far from all three obstacles: their wavefront leaves after the
+// records and the grid are in, having read 0.7 KB of its own (heights, records, root) and the shared 1 KB grid, and written nothing.
+__global__ void __launch_bounds__(64 * OBS_WAVES) qa_tsc_scan_obstacles_kernel(qa_tsc_obs_cfg c, qa_tsc_obs_io io, const float *__restrict__ obst_desc,
+                                                                               const float *__restrict__ obst_state) {
+    __shared__ float s_ob[OBS_WAVES][QA_OS_SLOTS * QA_OS_RECORD + QA_OS_SLOTS * 4];        // per env [3 records of 12 | 3 boxes of 4]
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int64_t N = c.num_envs;
+    const int64_t e_raw = (int64_t)blockIdx.x * OBS_WAVES + wave;
+    const bool valid = e_raw < N;
+    const int64_t e = valid ? e_raw : N - 1;          // a ragged tail stages the last env's records, takes part in the barrier and leaves
+    float *rec = s_ob[wave];
+    const float *rs = io.root_states + e * 13;
+    const float *od = obst_desc + e * (QA_OS_SLOTS * 8), *os = obst_state + e * (QA_OS_SLOTS * 4);
+
+    // ---- loads: root, the lane's three grid points and what the static launch measured at them, the lane's float of the records
+    const float r0 = rs[0], r1 = rs[1], rz = rs[2], q2 = rs[5], q3 = rs[6];
+    float hbx[3], hby[3], mh[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int p = lane + 64 * k < QA_TSC_NUM_SCAN ? lane + 64 * k : QA_TSC_NUM_SCAN - 1;
+        const float *hp = io.height_points + e * c.points_env_stride + p * c.point_stride;
+        hbx[k] = hp[0]; hby[k] = hp[1];
+        mh[k] = io.measured_heights[e * QA_TSC_NUM_SCAN + p];
+    }
+    if (lane < QA_OS_SLOTS * QA_OS_RECORD) rec[lane] = qa_os_record_float(od, os, lane / QA_OS_RECORD, lane % QA_OS_RECORD);
+    else if (lane < QA_OS_SLOTS * QA_OS_RECORD + QA_OS_SLOTS) qa_os_box(od, lane - QA_OS_SLOTS * QA_OS_RECORD, rec + QA_OS_SLOTS * QA_OS_RECORD + 4 * (lane - QA_OS_SLOTS * QA_OS_RECORD));
+    __syncthreads();
+    if (!valid) return;                               // (no barrier below: a wavefront may leave on its own)
+
+    // ---- how far the scan reaches from the root: the farthest grid point (a yaw rotation keeps its length), the same in every lane
+    float reach2 = fmaxf(fmaxf(hbx[0] * hbx[0] + hby[0] * hby[0], hbx[1] * hbx[1] + hby[1] * hby[1]), hbx[2] * hbx[2] + hby[2] * hby[2]);
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) reach2 = fmaxf(reach2, __shfl_xor(reach2, m, 64));
+    // the boxes are grown by QA_OS_BOX_PAD = 1 mm, the rotation's rounding is ~1e-6 m: a root farther than the reach from every box has no
+    // point inside a footprint (an empty slot's box lies 3e38 away)
+    bool near = false;
+#pragma unroll
+    for (int k = 0; k < QA_OS_SLOTS; ++k) {
+        const float *b = rec + QA_OS_SLOTS * QA_OS_RECORD + 4 * k;
+        const float dx = fmaxf(fmaxf(b[0] - r0, r0 - b[1]), 0.0f), dy = fmaxf(fmaxf(b[2] - r1, r1 - b[3]), 0.0f);
+        near = near || (b[0] <= b[1] && dx * dx + dy * dy <= reach2);
+    }
+    if (!near) return;                                // wave-uniform: root, boxes and reach are
+
+    const float qn = fmaxf(sqrtf(q2 * q2 + q3 * q3), 1e-9f);
+    const float qz = q2 / qn, qw = q3 / qn;
+    const float cl = c.clip_observations;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int p = lane + 64 * k;
+        const float bx = hbx[k], by = hby[k];
+        const float t0 = (0.0f - qz * by) * 2.0f, t1 = (qz * bx - 0.0f) * 2.0f;
+        const float wx = (bx + qw * t0) + (0.0f - qz * t1) + r0;
+        const float wy = (by + qw * t1) + (qz * t0 - 0.0f) + r1;
+        const qa_os_cover cv = qa_os_classify(rec, wx, wy);
+        if (cv.mode == QA_OS_NONE || p >= QA_TSC_NUM_SCAN) continue;
+        const float h = qa_os_floor(&cv, mh[k]);      // see-saw: the plank at the point itself; bar / tyre: the static measurement + q
+        io.measured_heights[e * QA_TSC_NUM_SCAN + p] = h;
+        io.obs_buf[e * QA_TSC_NUM_OBS + OFF_SCAN + p] = clampf(clampf((rz - 0.3f) - h, -1.0f, 1.0f), -cl, cl);
+        if (p == QA_TSC_NUM_SCAN / 2 + 1) {           // the scan's centre: phase B of the static kernel
+            const float root_h = rz - h;
+            const float v = clampf(c.root_height_obs ? root_h : 0.0f, -cl, cl);
+            io.obs_buf[e * QA_TSC_NUM_OBS + OFF_PRIV] = v;
+            io.obs_bbc_buf[e * QA_TSC_NUM_OBS_BBC + 57] = v;
+            io.obs_disc_buf[e * QA_TSC_NUM_OBS_DISC + 2] = root_h;
+        }
+    }
+}
+
 }  // namespace
 
 
@@ -696,6 +775,23 @@ int qa_tsc_observations(const qa_tsc_obs_cfg *cfg, const qa_tsc_obs_io *io, void
                        (hipStream_t)stream, c, *io);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_terr, sizeof(g_terr), "qa_tsc_observations: %s", hipGetErrorString(e)); return QA_E_DEVICE; }
+    return QA_OK;
+}
+
+
+// include/qa_tsc_scan_obstacles.h
+int qa_tsc_observations_obstacles(const qa_tsc_obs_cfg *cfg, const qa_tsc_obs_io *io, const qa_tsc_scan_obstacles *obst, void *stream) {
+    if (!cfg || !io) { snprintf(g_terr, sizeof(g_terr), "qa_tsc_observations_obstacles: null argument"); return QA_E_ARG; }
+    if (obst && (obst->obst_desc == nullptr) != (obst->obst_state == nullptr)) {
+        snprintf(g_terr, sizeof(g_terr), "qa_tsc_observations_obstacles: obst_desc and obst_state must be given together (one of them is null)"); return QA_E_ARG;
+    }
+    const int rc = qa_tsc_observations(cfg, io, stream);          // the static launch, and its argument checks
+    if (rc != QA_OK || !obst || !obst->obst_desc) return rc;
+    const qa_tsc_obs_cfg &c = *cfg;
+    hipLaunchKernelGGL(qa_tsc_scan_obstacles_kernel, dim3((unsigned)((c.num_envs + OBS_WAVES - 1) / OBS_WAVES)), dim3(64 * OBS_WAVES), 0,
+                       (hipStream_t)stream, c, *io, obst->obst_desc, obst->obst_state);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_terr, sizeof(g_terr), "qa_tsc_observations_obstacles: %s", hipGetErrorString(e)); return QA_E_DEVICE; }
     return QA_OK;
 }
 

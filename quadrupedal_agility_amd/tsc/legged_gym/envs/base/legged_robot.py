@@ -162,7 +162,14 @@ class LeggedRobot:
         gx, gy = torch.meshgrid(xs, ys, indexing="ij")                                     # _init_height_points (:1686-1706)
         self.num_height_points = gx.numel()
         self.height_points = torch.stack([gx.flatten(), gy.flatten(), torch.zeros_like(gx.flatten())], dim=1).contiguous()
-        self.bk.init_observations(self.height_samples, self.height_points, self.default_dof_pos, self.default_dof_pos_all, self.key_body_ids.tolist())
+        # obstacle.qa_scan_articulated (include/qa_tsc_scan_obstacles.h): the height scan reads the engine's live obstacle tensors, so the teacher
+        # measures the see-saw, bar and tyre where the physics has them.  Chosen here, before anything records a rollout: a recording bakes the launch in
+        live = {}
+        if getattr(cfg.obstacle, "qa_scan_articulated", False):
+            if not self.articulated:
+                raise ValueError("obstacle.qa_scan_articulated needs obstacle.articulated = True: without the bodies there is no joint state to measure")
+            live = dict(obst_desc=t["OBST_DESC"], obst_state=self.obst_state)
+        self.bk.init_observations(self.height_samples, self.height_points, self.default_dof_pos, self.default_dof_pos_all, self.key_body_ids.tolist(), **live)
         # (the extra reward terms, if any, are installed by the bookkeeping's constructor: before anything records a rollout)
         self.reward_scales = dict(self.bk.reward_scales)
         self.reward_names = [n for n in self.bk.reward_names if n != "termination"]

@@ -109,6 +109,7 @@ class LeggedRobotCfg(BaseConfig):
         frame_pos = [[[5.5, 1.0], [5.5, 5.0]], [[5.5, 5.0], [5.5, 9.0]], [[3.5, 9.0], [3.5, 5.0]],
                      [[3.5, 5.0], [3.5, 1.0]], [[1.5, 1.0], [1.5, 5.0]], [[1.5, 5.0], [1.5, 9.0]]]
         frame_ang = [90, 90, -90, -90, 90, 90]
+        qa_scan_articulated = False    # include/qa_tsc_scan_obstacles.h: the height scan measures see-saw, bar and tyre in their current joint state (needs obstacle.articulated)
 
     class commands:
         curriculum, max_curriculum = False, 1.0

@@ -9,7 +9,10 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ... import _capi, go2_limits
+from ... import _capi, _cdecl, go2_limits
+
+# include/qa_tsc_scan_obstacles.h: one struct for one entry point -- read from the headers directly, _capi's public names stay as they are
+QaTscScanObstacles = _cdecl.struct("qa_tsc_scan_obstacles")
 
 
 def coarse_depth_maps(height_samples, ceiling_samples, log2_block):
@@ -214,10 +217,24 @@ class TaskLevelBookkeeping:
         self.roll, self.pitch, self.yaw = self.rpy[:, 0], self.rpy[:, 1], self.rpy[:, 2]
         return self.reset_buf.nonzero(as_tuple=False).flatten() if want_ids else None          # nonzero() is a host sync
 
-    def init_observations(self, height_samples, height_points, default_dof_pos, default_dof_pos_all=None, key_body_ids=None):
+    def init_observations(self, height_samples, height_points, default_dof_pos, default_dof_pos_all=None, key_body_ids=None, obst_desc=None,
+                          obst_state=None):
         """Buffers and constants of compute_observations: the obstacle course's int16 height map, the reference's
-        `height_points` tensor (N,132,3) or one shared (132,2|3) grid, the default joint angles."""
+        `height_points` tensor (N,132,3) or one shared (132,2|3) grid, the default joint angles.
+        `obst_desc` (N,3,8) / `obst_state` (N,3,4): the engine's LIVE QA_T_OBST_DESC / QA_T_OBST_STATE tensors (obstacle.qa_scan_articulated,
+        include/qa_tsc_scan_obstacles.h) -- kept by reference, not copied: every scan reads the joints' current state."""
         dev, n, cfg = self.device, self.num_envs, self.cfg
+        if (obst_desc is None) != (obst_state is None):
+            raise ValueError("init_observations: obst_desc and obst_state go together")
+        self._scan_obst = None
+        if obst_desc is not None:
+            if not hasattr(self.lib, self.api.prefix + "tsc_observations_obstacles"):
+                raise NotImplementedError("obstacle.qa_scan_articulated needs the HIP library (qa_tsc_observations_obstacles); this backend has no "
+                                          f"{self.api.prefix}tsc_observations_obstacles: the scan would measure the static map")
+            for name, t, shape in (("obst_desc", obst_desc, (n, 3, 8)), ("obst_state", obst_state, (n, 3, 4))):
+                if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device.type != dev.type or not t.is_contiguous():
+                    raise ValueError(f"init_observations: {name} must be a contiguous float32 {shape} tensor on {dev}")
+            self._scan_obst = (obst_desc, obst_state)
         self.height_samples = height_samples.to(dev, torch.int16).contiguous()
         self.height_points = height_points.to(dev, torch.float32).contiguous()
         if self.height_points.shape[-2] != _capi.TSC_NUM_SCAN:
@@ -266,7 +283,11 @@ class TaskLevelBookkeeping:
         io = _capi.QaTscObsIo()
         for name in _capi.TSC_OBS_IO_FIELDS:
             setattr(io, name, members[name].data_ptr())
-        self.api.launch("tsc_observations", C.byref(self._ocfg), C.byref(io), on=self.device)
+        if self._scan_obst is not None:
+            ob = QaTscScanObstacles(self._scan_obst[0].data_ptr(), self._scan_obst[1].data_ptr())
+            self.api.launch("tsc_observations_obstacles", C.byref(self._ocfg), C.byref(io), C.byref(ob), on=self.device)
+        else:
+            self.api.launch("tsc_observations", C.byref(self._ocfg), C.byref(io), on=self.device)
         return self.obs_buf
 
     def init_depth(self, height_samples, ceiling_samples, camera_pitch, seed=1, env_id_offset=0, obst_desc=None, obst_state=None):

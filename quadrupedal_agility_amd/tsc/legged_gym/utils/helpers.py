@@ -65,6 +65,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             env_cfg.asset.qa_self_collision_thighs = True
         if getattr(args, "depth_articulated", False):
             env_cfg.depth.qa_articulated = True
+        if getattr(args, "scan_articulated", False):
+            env_cfg.obstacle.qa_scan_articulated = True
         for item in getattr(args, "reward_scale", None) or []:
             name, eq, value = item.partition("=")
             if not hasattr(env_cfg.rewards.scales, name):
@@ -124,6 +126,7 @@ def get_args(argv=None):
     p.add_argument("--self_collision_hips", action="store_true", default=False, help="asset.qa_self_collision_hips = True: a front calf collides with the rear hip of its side (a hip contact ends the episode, as in the reference)")
     p.add_argument("--self_collision_thighs", action="store_true", default=False, help="asset.qa_self_collision_thighs = True: each calf of a front / rear pair of legs collides with the other leg's thigh (the collision penalty counts it; pass --self_collision_hips too)")
     p.add_argument("--depth_articulated", action="store_true", default=False, help="depth.qa_articulated = True: the depth camera renders the see-saw, bar and tyre in their current joint state (with --use_camera)")
+    p.add_argument("--scan_articulated", action="store_true", default=False, help="obstacle.qa_scan_articulated = True: the teacher's height scan measures the see-saw, bar and tyre in their current joint state")
     p.add_argument("--reward_scale", action="append", default=[], metavar="NAME=VALUE",
                    help="rewards.scales.NAME = VALUE for any of the reference's 22 terms (repeatable), e.g. --reward_scale torques=-1e-5")
     p.add_argument("--physics_engine", default="qa")

@@ -12,7 +12,9 @@ classes and its constants), so the same file describes any commit's binding, how
               (qa_last_error, qa_abi_version: no arguments, restype only)
   structs     for every ctypes.Structure of _capi each field's name, offset, size and type, and the total size
   constants   every public int, float, str, list, tuple and dict (with the container's type: a tuple is not a list)
-LIB_PATH is left out: it is where this checkout lies, not part of the ABI."""
+LIB_PATH is left out: it is where this checkout lies, not part of the ABI.
+The headers of _capi._RECORDED_APART have records of their own beside it, in the same form (dump_apart): their entry points, with the header's
+name as the list, and their structs.  --write and --check go over all of them."""
 import ctypes as C
 import json
 import os
@@ -44,6 +46,11 @@ def type_name(t):
     return t.__name__ if issubclass(t, C.Structure) else kind(t)
 
 
+def struct_record(cls):
+    return {"size": C.sizeof(cls), "fields": [{"name": f, "offset": getattr(cls, f).offset, "size": getattr(cls, f).size, "type": type_name(t)}
+                                              for f, t in cls._fields_]}
+
+
 def dump():
     sys.path.insert(0, ROOT)
     from quadrupedal_agility_amd import _capi
@@ -60,8 +67,7 @@ def dump():
         if name.startswith("_") or name in ("LIB_PATH", "ABI_SYMBOLS", "EXTENSION_SYMBOLS"):
             continue
         if isinstance(v, type) and issubclass(v, C.Structure):
-            structs[name] = {"size": C.sizeof(v), "fields": [{"name": f, "offset": getattr(v, f).offset, "size": getattr(v, f).size, "type": type_name(t)}
-                                                             for f, t in v._fields_]}
+            structs[name] = struct_record(v)
         elif isinstance(v, (int, float, str)) and not isinstance(v, bool):
             constants[name] = v
         elif isinstance(v, (list, tuple)):
@@ -69,6 +75,33 @@ def dump():
         elif isinstance(v, dict):
             constants[name] = {"dict": [[k, x] for k, x in v.items()]}
     return {"functions": functions, "structs": structs, "constants": constants}
+
+
+def dump_apart():
+    """{record file under tests/golden: dump} for the headers of _capi._RECORDED_APART; a struct qa_some_name is recorded as QaSomeName"""
+    sys.path.insert(0, ROOT)
+    from quadrupedal_agility_amd import _capi, _cdecl
+    lib = _capi.load_library()
+    out = {}
+    for header, (record, cnames) in _capi._RECORDED_APART.items():
+        functions = {}
+        for h, name, _, _ in _cdecl.prototypes:
+            if h == header:
+                f = getattr(lib, "qa_" + name)
+                functions[name] = {"list": header, "restype": kind(f.restype), "args": ["ptr" if kind(t) == "str" else kind(t) for t in f.argtypes]}
+        structs = {"".join(p.title() for p in c.split("_")): struct_record(_cdecl.struct(c)) for c in cnames}
+        out[record] = {"functions": functions, "structs": structs, "constants": {}}
+    return out
+
+
+def merged(d, apart):
+    """the record of the whole binding: d with the records of dump_apart() added to it"""
+    out = {k: dict(v) for k, v in d.items()}
+    for rec in apart.values():
+        for k, v in rec.items():
+            assert not set(v) & set(out[k]), "a name is recorded twice"
+            out[k].update(v)
+    return out
 
 
 def text(d):
@@ -84,13 +117,15 @@ def differences(a, b, path=""):
 
 
 if __name__ == "__main__":
-    d = dump()
+    d, apart = dump(), dump_apart()
+    files = [(GOLDEN, d)] + [(os.path.join(os.path.dirname(GOLDEN), record), rec) for record, rec in apart.items()]
     if "--write" in sys.argv:
-        with open(GOLDEN, "w") as f:
-            f.write(text(d))
+        for path, rec in files:
+            with open(path, "w") as f:
+                f.write(text(rec))
     elif "--check" in sys.argv:
-        diff = differences(d, json.load(open(GOLDEN)))
-        print("\n".join(diff) if diff else "equal to tests/golden/abi.json")
+        diff = [f"{os.path.basename(path)}{line}" for path, rec in files for line in differences(rec, json.load(open(path)))]
+        print("\n".join(diff) if diff else "equal to tests/golden/abi.json and the records beside it")
         sys.exit(1 if diff else 0)
     else:
-        sys.stdout.write(text(d))
+        sys.stdout.write(text(merged(d, apart)))
