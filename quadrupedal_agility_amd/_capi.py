@@ -86,6 +86,9 @@ ABI_SYMBOLS = [name for header, name, _, _ in H.prototypes if header == "qa_sim.
 # record of their own beside it ({header: (record under tests/golden/, the header's structs)}; tools/abi_dump.py writes and checks both):
 # their entry points are bound like every other (bind_extensions goes by the headers), their structs are read by the module that uses them.
 _RECORDED_APART = {"qa_tsc_scan_obstacles.h": ("abi_scan_obstacles.json", ("qa_tsc_scan_obstacles",))}
+# The same for the env engine's extension headers that came after abi.json was last written.  Their entry points are EXTENSION_SYMBOLS like those of
+# the engine's other extension headers; tools/abi_dump.py keeps them out of abi.json's record and writes / checks the record named here.
+_RECORDED_APART_ENGINE = {"qa_sim_actuators.h": ("abi_actuators.json", ("qa_actuators",))}
 EXTENSION_SYMBOLS = [name for header, name, _, _ in H.prototypes if header != "qa_sim.h" and header not in _RECORDED_APART]
 
 
@@ -104,7 +107,7 @@ def bind(lib, prefix):
 
 
 def bind_extensions(lib, prefix="qa_"):
-    """Entry points declared in the extension headers next to include/qa_sim.h (EXTENSION_SYMBOLS and those of _RECORDED_APART): exported by
+    """Entry points declared in the extension headers next to include/qa_sim.h (EXTENSION_SYMBOLS and those of _RECORDED_APART*): exported by
     the HIP library only, no oracle twin, not part of ABI_SYMBOLS."""
     return _bind(lib, prefix, True)
 

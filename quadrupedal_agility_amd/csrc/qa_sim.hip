@@ -21,21 +21,34 @@
 #include "../../include/qa_sim_rewards.h"
 #include "../../include/qa_sim_selfcol.h"
 #include "../../include/qa_sim_reset.h"
+#include "../../include/qa_sim_actuators.h"
 // This file is compiled once per self-collision level, and QA_SCH_LEVEL says which translation unit this is.  On its own (level 0) it is the
 // library's env engine: every kernel as it always was, the host side and the C ABI.  qa_sim_selfcol.hip (level 1, qa_set_self_collision_hips) and
 // qa_sim_selfcol_thighs.hip (level 2, qa_set_self_collision_thighs on top) set the level and include this file; there it contributes the kernel
 // templates and the level's launchers (qa_env_launchers, below the kernels), which instantiate the kernels that run physics with SCH = QA_SCH_LEVEL.
 // Instantiating those HERE, next to the others, changed the code the compiler generated for the existing kernels (same instructions, another
-// schedule and register assignment), and those are to stay exactly as they are.  What only level 0 has stands in `#if QA_SCH_LEVEL == 0`.
+// schedule and register assignment), and those are to stay exactly as they are.  What only level 0 has stands in `#if QA_MAIN_UNIT`.
 #ifndef QA_SCH_LEVEL
 #define QA_SCH_LEVEL 0
 #endif
+// One more unit of the same kind: qa_sim_actuators.hip sets QA_ACTUATORS and includes this file; there it contributes the step kernels that take the
+// actuator model of include/qa_sim_actuators.h from their launch arguments (ACT = 1, self-collision level 0 only) and their launchers.  QA_MAIN_UNIT
+// is the unit that also carries the host side and the C ABI.
+#ifndef QA_ACTUATORS
+#define QA_ACTUATORS 0
+#endif
+#if QA_ACTUATORS && QA_SCH_LEVEL != 0
+#error "the actuator unit is built at self-collision level 0 only"
+#endif
+#define QA_MAIN_UNIT (QA_SCH_LEVEL == 0 && !QA_ACTUATORS)
 // A level's cross-unit symbols: the plain name at level 0, name_sch<level> above it.  A code object has its own constant memory, so every level
 // keeps its own copy of the table.  The device symbols keep external linkage: as `static __constant__` the table is reached through a GOT load
 // under -fPIC (an s_load_dwordx2 of the address instead of a pc-relative one), which changes the code of all of the unit's kernels.
 #define QA_LVL_N_(name, n) name##_sch##n
 #define QA_LVL_N(name, n) QA_LVL_N_(name, n)
-#if QA_SCH_LEVEL == 0
+#if QA_ACTUATORS
+#define QA_LVL(name) name##_act
+#elif QA_SCH_LEVEL == 0
 #define QA_LVL(name) name
 #else
 #define QA_LVL(name) QA_LVL_N(name, QA_SCH_LEVEL)
@@ -142,6 +155,8 @@ struct qa_sim {
     int lean = 0;                  // qa_set_lean_exports
     int sc_level = 0;              // SCH level of the step / simulate kernels (index into k_levels): 1 qa_set_self_collision_hips, 2 qa_set_self_collision_thighs on top of it
     int num_cus = 256;             // compute units of the device the arena lives on (launch_env_step: helper wavefronts by launch size)
+    int act_type = -1;             // qa_set_actuators: QA_ACTUATOR_*, -1 = off (the kernels that read cfg.kp / cfg.kd); on = the launchers of k_levels[QA_ACT_UNIT]
+    float *act_tbl = nullptr;      // ... and its device table kp[12] kd[12], owned by the handle
     qa_config cfg;
     Layout L;
     char *arena;
@@ -152,7 +167,7 @@ struct qa_sim {
 
 struct MocapIdx { int32_t on; };      // clips uploaded; the per-gait clip ranges live in column 5 of QA_T_MOCAP_CLIPS
 
-#if QA_SCH_LEVEL == 0
+#if QA_MAIN_UNIT
 thread_local char qa_err_buf[512] = "";      // shared with qa_learner.hip
 #else
 extern thread_local char qa_err_buf[512];
@@ -388,6 +403,15 @@ QA_DEV void stage_obstacles(const Ptrs &p, int env, int leg, float *rec, float a
 
 // ------------------------------------------------------------------ the fused env step
 struct StepArgs { qa_config c; Ptrs p; MocapIdx mi; const float *actions; int delay; int64_t step; int64_t *step_ptr; long long *prof; };
+// qa_set_actuators (include/qa_sim_actuators.h): what the ACT instantiations of the step kernel get on top -- the control type and the handle's
+// device table kp[12] kd[12] (read per lane by joint, which a kernel-argument array could not be without a private copy).  The others keep
+// StepArgs as their one argument, so their kernel-argument segment is what it was.
+struct ActArgs { const float *gains; int32_t type; float inv_dt; };     // inv_dt: fp32(1 / cfg.sim_dt), for the V law's quotient
+struct StepArgsAct { StepArgs s; ActArgs act; };
+template <int ACT> struct StepArgsOf { typedef StepArgs type; };
+template <> struct StepArgsOf<1> { typedef StepArgsAct type; };
+__device__ __forceinline__ const StepArgs &step_args(const StepArgs &a) { return a; }
+__device__ __forceinline__ const StepArgs &step_args(const StepArgsAct &a) { return a.s; }
 // LEAN (qa_set_lean_exports, MODE 0 only): bit 0 = do not write the tensors nothing between two steps of a training run reads (seam-1 / logging
 // exports: CONTACT_FORCES, RIGID_BODY_POS, TORQUES, TORQUES_ORG, ACTIONS, BASE_LIN_VEL, BASE_ANG_VEL, PROJECTED_GRAVITY, RPY, FEET_FORCE,
 // CONTACT_FILT, SCAN_HEIGHT) and keep only the two newest slots of the action ring (all a delay <= 1 can reach); bit 1 = no discriminator
@@ -982,8 +1006,39 @@ QA_DEV void shift_history_store(const Ptrs &p, int bix, int lane, int N, float (
 // SCH = 1 (qa_set_self_collision_hips): the substeps also collide each front calf with the rear hip of its side; one more 16-byte-aligned row record
 // per lane in LDS (46 -> 52 KB of private slots per workgroup).  SCH = 2 (qa_set_self_collision_thighs): and each calf of a front / rear pair with the
 // other leg's thigh; two more records (61 KB).  The SCH = 0 instantiations are the kernels as they were.
-template <bool PLANE, int LPE, int MODE = 0, int LEAN = 0, int HELP = 0, int XR = 0, int SCH = 0>
-__global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(StepArgs a) {
+// ACT = 1 (qa_set_actuators, include/qa_sim_actuators.h; qa_sim_actuators.hip instantiates these): the substeps' torque law and its per-joint gains
+// come from the launch arguments.  The lane's gain pairs and the V law's last_qd are three more 16-byte records of its private LDS slots, behind
+// the 180 floats of SCH = 0 (lane stride 49 records, odd again: 46 -> 50 KB per workgroup), unparked per substep like the other per-step constants.
+#define QA_PRIV_ACT 180
+#define QA_PRIV_FLOATS_ACT 196
+QA_DEV void priv_park_act(float *priv, const float *gp, const float *gd, const float *lqd) {
+    f4 *q = reinterpret_cast<f4 *>(priv + QA_PRIV_ACT);
+    q[0] = f4{gp[0], gp[1], gp[2], gd[0]}; q[1] = f4{gd[1], gd[2], lqd[0], lqd[1]}; q[2] = f4{lqd[2], 0.f, 0.f, 0.f};
+}
+QA_DEV void priv_unpark_act(const float *priv, float *gp, float *gd, float *lqd) {
+    const f4 *q = reinterpret_cast<const f4 *>(priv + QA_PRIV_ACT);
+    const f4 a = q[0], b = q[1], c = q[2];
+    gp[0] = a.x; gp[1] = a.y; gp[2] = a.z; gd[0] = a.w; gd[1] = b.x; gd[2] = b.y; lqd[0] = b.z; lqd[1] = b.w; lqd[2] = c.x;
+}
+// _compute_torques (bbc/legged_gym/envs/base/legged_robot.py:563-575) for one joint, every operation rounded on its own and in the reference's
+// order (fp contraction is off in here).  `type` is uniform over the launch.  x / dt: the unit is compiled with approximate division, so the
+// quotient is one Newton step on x * (1 / dt) with the remainder taken exactly by an fma -- correctly rounded, as torch's division is.
+QA_DEV float actuator_torque(int type, float as, float q0, float q, float qd, float gp, float gd, float lqd, float dt, float inv_dt) {
+#pragma clang fp contract(off)
+    if (type == QA_ACTUATOR_T) return as;
+    if (type == QA_ACTUATOR_V) {
+        const float x = gd * (qd - lqd);
+        const float y = x * inv_dt;
+        const float quot = fmaf(fmaf(-y, dt, x), inv_dt, y);
+        return gp * (as - qd) - quot;
+    }
+    return gp * (as + q0 - q) - gd * qd;
+}
+
+template <bool PLANE, int LPE, int MODE = 0, int LEAN = 0, int HELP = 0, int XR = 0, int SCH = 0, int ACT = 0>
+__global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(typename StepArgsOf<ACT>::type ka) {
+    static_assert(ACT == 0 || SCH == 0, "the actuator instantiations exist at self-collision level 0 only");
+    const StepArgs &a = step_args(ka);
     static_assert(XR == 0 || MODE == 0, "the extra reward terms belong to the behaviour-level post-physics phase");
     static_assert(LEAN == 0 || MODE == 0, "the task-level tree reads every tensor the physics step exports");
     static_assert(HELP == 0 || (PLANE && MODE == 0), "helper wavefronts: the behaviour-level plane kernels");
@@ -1000,7 +1055,7 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
     // holds -- 160 KB per CU -- and with it the throughput once there are more workgroups than CUs):
     //   physics phase:      per-lane private slots | terrain windows (height field only)
     //   observation phase:  per-env staging | OBS_GROUP assembled observation rows
-    constexpr int PRIV_FLOATS = QA_PRIV_FLOATS_OF(SCH);
+    constexpr int PRIV_FLOATS = ACT ? QA_PRIV_FLOATS_ACT : QA_PRIV_FLOATS_OF(SCH);
     constexpr int U_PHYS = PRIV_FLOATS * QA_PRIV_STRIDE + (PLANE ? 0 : EPB * QA_PATCH * QA_PATCH + EPB * QA_OB_LDS);
     constexpr int U_OBS = EPB * S_ENV + OBS_GROUP * S_ROW;
     constexpr int U_ALL = ((U_PHYS > U_OBS ? U_PHYS : U_OBS) + 3) & ~3;
@@ -1027,7 +1082,7 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
         PhysParams P; P.dt = c.sim_dt; P.gz = c.gravity_z; P.contact_offset = c.contact_offset; P.max_depen = c.max_depenetration_velocity;
         P.ground_friction = c.ground_friction; P.iters = c.solver_iterations; P.slots = c.contact_slots == 1 ? 1 : 2; P.self_collision = c.self_collision;
         TerrainView T = terrain_view(c, a.p, s_u);
-        float *priv = priv_of<SCH>(s_u, tix);
+        float *priv = ACT ? s_u + tix * QA_PRIV_FLOATS_ACT : priv_of<SCH>(s_u, tix);
         EnvState st; ContactOut co;
         float fimp[3] = {0.f, 0.f, 0.f}, tau[3] = {0.f, 0.f, 0.f};
         // The history shift of the observation rows (513 floats per env read and written, 3/4 of the launch's bytes) is pure data movement: the bias
@@ -1179,8 +1234,22 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
     // ---- decimation x (PD torque -> physics)   legged_robot.py:101-106, :547-579
     // per-step constants are parked in per-lane LDS slots between substeps so that they do not hold VGPRs
     // through the substep (the substep alone needs ~340 registers)
-    float *priv = priv_of<SCH>(s_priv, tix);
+    float *priv = ACT ? s_priv + tix * QA_PRIV_FLOATS_ACT : priv_of<SCH>(s_priv, tix);
     priv_park(priv, act, sp, sd, binert);
+    if constexpr (ACT != 0) {
+        // the lane's three gain pairs (P with randomize_motor: times the motor strength, the product the reference forms first) and, for the V
+        // law, last_qd: LAST_DOF_VEL as the step finds it, or (MODE 1) the velocity the step starts from -- read once, held over the substeps
+        float gp[3], gd[3], lqd[3];
+        const bool strength = ka.act.type == QA_ACTUATOR_P && c.randomize_motor;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float kpj = ka.act.gains[3 * leg + k], kdj = ka.act.gains[12 + 3 * leg + k];
+            gp[k] = strength ? sp[k] * kpj : kpj;
+            gd[k] = strength ? sd[k] * kdj : kdj;
+            lqd[k] = MODE == 1 ? st.qd[k] : (ka.act.type == QA_ACTUATOR_V ? p.last_dof_vel[(int64_t)env * 12 + 3 * leg + k] : 0.f);
+        }
+        priv_park_act(priv, gp, gd, lqd);
+    }
     float tau[3], tau_org[3];
     ContactOut co;
     float fimp[3];
@@ -1208,11 +1277,15 @@ __global__ void __launch_bounds__(QA_BLOCK * (HELP ? 3 : 1)) qa_env_step_kernel(
         if (HELP) { mail_put_state(mail, st); __syncthreads(); }
         float bi[10], pa[3], psp[3], psd[3];
         priv_unpark(priv, pa, psp, psd, bi);
+        float agp[3], agd[3], alqd[3];
+        if constexpr (ACT != 0) priv_unpark_act(priv, agp, agd, alqd);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             float as = pa[k] * c.action_scale;
             if (k == 0) as *= c.hip_scale_reduction;
-            float t = c.randomize_motor ? psp[k] * c.kp * (as + q0[k] - st.q[k]) - psd[k] * c.kd * st.qd[k]
+            float t;
+            if constexpr (ACT != 0) t = actuator_torque(ka.act.type, as, q0[k], st.q[k], st.qd[k], agp[k], agd[k], alqd[k], c.sim_dt, ka.act.inv_dt);
+            else t = c.randomize_motor ? psp[k] * c.kp * (as + q0[k] - st.q[k]) - psd[k] * c.kd * st.qd[k]
                                         : c.kp * (as + q0[k] - st.q[k]) - c.kd * st.qd[k];
             tau_org[k] = t;
             float lim = tbl[T_EFFORT + k];
@@ -1368,7 +1441,7 @@ __device__ __forceinline__ float normal_from(float u1, float u2) {
     return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
 
-#if QA_SCH_LEVEL == 0
+#if QA_MAIN_UNIT
 struct BaseConst { float m, com[3], I[6]; };
 
 __global__ void qa_init_kernel(qa_config c, Ptrs p, BaseConst bc) {
@@ -1443,7 +1516,7 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_reset_all_kernel(qa_config c, Ptr
     for (int i = leg; i < 570; i += 4) p.obs[(int64_t)env * QA_NUM_OBS + 90 + i] = 0.f;
 }
 
-#endif   // QA_SCH_LEVEL == 0
+#endif   // QA_MAIN_UNIT
 
 template <bool PLANE, int LPE, int SCH = 0>
 __global__ void __launch_bounds__(QA_BLOCK) qa_simulate_kernel(qa_config c, Ptrs p, const float *torques, const uint8_t *cond) {
@@ -1522,27 +1595,36 @@ __global__ void __launch_bounds__(QA_BLOCK) qa_simulate_kernel(qa_config c, Ptrs
     }
 }
 
-// ------------------------------------------------------------------ this level's launchers
-// Every translation unit (see the top of this file) defines the same four host functions over its SCH = QA_SCH_LEVEL instantiations and exports
-// them as ONE object, QA_LVL(qa_env_level); the level-0 host side reaches the kernels that run physics through k_levels[] only.  A new launch
-// axis is added here, once; a new level is a two-line .hip file and one more entry of k_levels.
+// ------------------------------------------------------------------ this unit's launchers
+// Every translation unit (see the top of this file) defines the same four host functions over its SCH = QA_SCH_LEVEL, ACT = QA_ACTUATORS
+// instantiations and exports them as ONE object, QA_LVL(qa_env_level); the host side of the main unit reaches the kernels that run physics through
+// k_levels[] only.  A new launch axis is added here, once; a new level is a two-line .hip file and one more entry of k_levels.  The actuator unit
+// (qa_sim_actuators.hip) is such an entry: its step kernels take StepArgsAct, and it has no simulate of its own (the caller brings the torques).
 struct qa_env_launchers {
     int (*upload_table)(const float *tbl);
-    void (*env_step)(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a);
-    void (*physics_step)(bool hf, int blocks, hipStream_t st, const StepArgs &a);
+    void (*env_step)(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a, const ActArgs &act);
+    void (*physics_step)(bool hf, int blocks, hipStream_t st, const StepArgs &a, const ActArgs &act);
     void (*simulate)(bool hf, int blocks, hipStream_t st, const qa_config &c, const Ptrs &p, const float *torques, const uint8_t *cond);
 };
 
 static int lvl_upload_table(const float *tbl) {
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(QA_LVL(c_tbl)), tbl, sizeof(float) * QA_TBL_FLOATS);
-    return e == hipSuccess ? QA_OK : fail_hip(e, QA_SCH_LEVEL == 0 ? "hipMemcpyToSymbol(c_tbl)" : "hipMemcpyToSymbol(c_tbl, self-collision kernels)");
+    return e == hipSuccess ? QA_OK : fail_hip(e, QA_ACTUATORS ? "hipMemcpyToSymbol(c_tbl, actuator kernels)" : QA_SCH_LEVEL == 0 ? "hipMemcpyToSymbol(c_tbl)" : "hipMemcpyToSymbol(c_tbl, self-collision kernels)");
 }
 
+// the one argument of this unit's step kernels: StepArgs, in the actuator unit with the actuator model behind it
+#if QA_ACTUATORS
+#define QA_STEP_ARG(name) const StepArgsAct name{a, act}
+#else
+#define QA_STEP_ARG(name) const StepArgs &name = a; (void)act
+#endif
+
 // helpers: two helper wavefronts per workgroup, plane kernels only; xr: qa_set_extra_rewards, the XR instantiations
-static void lvl_env_step(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a) {
+static void lvl_env_step(bool hf, int lean, bool helpers, bool xr, int blocks, hipStream_t st, const StepArgs &a, const ActArgs &act) {
+    QA_STEP_ARG(ka);
 #define QA_LAUNCH_STEP(PLANE_, LEAN_, HELP_) do { \
-        if (xr) hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 1, QA_SCH_LEVEL>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); \
-        else hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 0, QA_SCH_LEVEL>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, a); } while (0)
+        if (xr) hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 1, QA_SCH_LEVEL, QA_ACTUATORS>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, ka); \
+        else hipLaunchKernelGGL((qa_env_step_kernel<PLANE_, 4, 0, LEAN_, HELP_, 0, QA_SCH_LEVEL, QA_ACTUATORS>), dim3(blocks), dim3((HELP_ ? 3 : 1) * QA_BLOCK), 0, st, ka); } while (0)
     if (!hf && helpers) {
         if (lean == 3) QA_LAUNCH_STEP(true, 3, 1);
         else if (lean == 1) QA_LAUNCH_STEP(true, 1, 1);
@@ -1562,24 +1644,35 @@ static void lvl_env_step(bool hf, int lean, bool helpers, bool xr, int blocks, h
 #undef QA_LAUNCH_STEP
 }
 
-static void lvl_physics_step(bool hf, int blocks, hipStream_t st, const StepArgs &a) {
-    if (hf) hipLaunchKernelGGL((qa_env_step_kernel<false, 4, 1, 0, 0, 0, QA_SCH_LEVEL>), dim3(blocks), dim3(QA_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 1, 0, 0, 0, QA_SCH_LEVEL>), dim3(blocks), dim3(QA_BLOCK), 0, st, a);
+static void lvl_physics_step(bool hf, int blocks, hipStream_t st, const StepArgs &a, const ActArgs &act) {
+    QA_STEP_ARG(ka);
+    if (hf) hipLaunchKernelGGL((qa_env_step_kernel<false, 4, 1, 0, 0, 0, QA_SCH_LEVEL, QA_ACTUATORS>), dim3(blocks), dim3(QA_BLOCK), 0, st, ka);
+    else hipLaunchKernelGGL((qa_env_step_kernel<true, 4, 1, 0, 0, 0, QA_SCH_LEVEL, QA_ACTUATORS>), dim3(blocks), dim3(QA_BLOCK), 0, st, ka);
 }
 
+#if !QA_ACTUATORS
 static void lvl_simulate(bool hf, int blocks, hipStream_t st, const qa_config &c, const Ptrs &p, const float *torques, const uint8_t *cond) {
     if (hf) hipLaunchKernelGGL((qa_simulate_kernel<false, 4, QA_SCH_LEVEL>), dim3(blocks), dim3(QA_BLOCK), 0, st, c, p, torques, cond);
     else hipLaunchKernelGGL((qa_simulate_kernel<true, 4, QA_SCH_LEVEL>), dim3(blocks), dim3(QA_BLOCK), 0, st, c, p, torques, cond);
 }
+#endif
 
 extern const qa_env_launchers QA_LVL(qa_env_level);
 #ifndef __HIP_DEVICE_COMPILE__       // host data: the device pass would emit a constant with external linkage into the code object too
+#if QA_ACTUATORS
+const qa_env_launchers QA_LVL(qa_env_level) = {lvl_upload_table, lvl_env_step, lvl_physics_step, nullptr};
+#else
 const qa_env_launchers QA_LVL(qa_env_level) = {lvl_upload_table, lvl_env_step, lvl_physics_step, lvl_simulate};
 #endif
+#endif
 
-#if QA_SCH_LEVEL == 0
-extern const qa_env_launchers QA_LVL_N(qa_env_level, 1), QA_LVL_N(qa_env_level, 2);      // qa_sim_selfcol.hip, qa_sim_selfcol_thighs.hip
-static const qa_env_launchers *const k_levels[3] = {&qa_env_level, &QA_LVL_N(qa_env_level, 1), &QA_LVL_N(qa_env_level, 2)};    // by qa_sim::sc_level
+#if QA_MAIN_UNIT
+extern const qa_env_launchers QA_LVL_N(qa_env_level, 1), QA_LVL_N(qa_env_level, 2), qa_env_level_act;      // qa_sim_selfcol.hip, qa_sim_selfcol_thighs.hip, qa_sim_actuators.hip
+#define QA_ACT_UNIT 3
+static const qa_env_launchers *const k_levels[4] = {&qa_env_level, &QA_LVL_N(qa_env_level, 1), &QA_LVL_N(qa_env_level, 2), &qa_env_level_act};    // by qa_sim::sc_level; [QA_ACT_UNIT] while qa_set_actuators is on
+// the unit whose step kernels a handle launches (qa_simulate stays with sc_level: the actuator unit has none)
+static const qa_env_launchers *step_unit(const qa_sim *s) { return k_levels[s->act_type >= 0 ? QA_ACT_UNIT : s->sc_level]; }
+static ActArgs act_args(const qa_sim *s) { ActArgs x; x.gains = s->act_tbl; x.type = s->act_type; x.inv_dt = (float)(1.0 / (double)s->cfg.sim_dt); return x; }
 
 // ------------------------------------------------------------------ fused GAE (rollout_storage.py:97-111)
 // pass 1: one lane per env, reverse scan over T (coalesced across envs); per-block partial sums in double.
@@ -1730,7 +1823,7 @@ int qa_create(const qa_config *cfg, void *arena, int64_t arena_bytes, void *stre
     return QA_OK;
 }
 
-int qa_destroy(qa_sim *s) { delete s; return QA_OK; }
+int qa_destroy(qa_sim *s) { if (s && s->act_tbl) (void)hipFree(s->act_tbl); delete s; return QA_OK; }
 
 int qa_set_mocap(qa_sim *s, const float *frames, int32_t nf, const double *clips, int32_t nc, const int32_t first[QA_NUM_GAITS + 1], void *stream) {
     if (!s || !frames || !clips || !first || nf <= 0 || nf > s->cfg.num_mocap_frames || nc <= 0 || nc > QA_MAX_MOCAP_CLIPS) return QA_E_ARG;
@@ -1764,7 +1857,7 @@ static void launch_env_step(qa_sim *s, const StepArgs &a, hipStream_t st) {
     // 0 = never (the one-wavefront kernels, A/B runs), 1 = always, unset = by launch size
     static const int helpers_switch = [] { const char *e = getenv("QA_ENV_HELPERS"); return e ? (atoi(e) != 0 ? 1 : 0) : QA_ENV_HELPERS_DEFAULT; }();
     const bool helpers = helpers_switch == 1 || (helpers_switch < 0 && blocks <= s->num_cus);
-    k_levels[s->sc_level]->env_step(hf, s->lean, helpers, s->p.xr_sums != nullptr, blocks, st, a);
+    step_unit(s)->env_step(hf, s->lean, helpers, s->p.xr_sums != nullptr, blocks, st, a, act_args(s));
 }
 
 int qa_set_lean_exports(qa_sim *s, int32_t mask) {
@@ -1795,6 +1888,10 @@ static int sc_level_settable(const qa_sim *s, int on, const char *fn, const char
     if (!s) return QA_E_ARG;
     if (on && !s->cfg.self_collision) {
         snprintf(g_err, sizeof(g_err), "%s: the handle was created with self_collision = 0 (the %s rows belong to the self-collision model)", fn, rows);
+        return QA_E_ARG;
+    }
+    if (on && s->act_type >= 0) {
+        snprintf(g_err, sizeof(g_err), "%s: qa_set_actuators is on, and the actuator kernels exist without the %s rows only", fn, rows);
         return QA_E_ARG;
     }
     return QA_OK;
@@ -1830,6 +1927,27 @@ int qa_set_extra_rewards(qa_sim *s, const qa_extra_rewards *x) {
     p.xr_scan = x->scan_offsets; p.xr_scan_n = x->num_scan_points;
     for (int i = 0; i < QA_NUM_EXTRA_REWARDS; ++i) p.xr_scale[i] = x->scale_dt[i];
     p.xr_target = x->base_height_target; p.xr_max_force = x->max_contact_force; p.xr_dt = x->step_dt;
+    return QA_OK;
+}
+
+int qa_set_actuators(qa_sim *s, const qa_actuators *x) {
+    if (!s) return QA_E_ARG;
+    if (!x) { s->act_type = -1; return QA_OK; }          // the table stays with the handle until qa_destroy
+    if (x->control_type != QA_ACTUATOR_P && x->control_type != QA_ACTUATOR_V && x->control_type != QA_ACTUATOR_T) {
+        snprintf(g_err, sizeof(g_err), "qa_set_actuators: control_type must be QA_ACTUATOR_P, _V or _T (0, 1, 2), got %d", (int)x->control_type); return QA_E_ARG;
+    }
+    for (int j = 0; j < QA_NUM_DOF; ++j) if (!isfinite(x->kp[j]) || !isfinite(x->kd[j])) {
+        snprintf(g_err, sizeof(g_err), "qa_set_actuators: the gains of joint %d are not finite (%g, %g)", j, (double)x->kp[j], (double)x->kd[j]); return QA_E_ARG;
+    }
+    if (s->sc_level != 0) {
+        snprintf(g_err, sizeof(g_err), "qa_set_actuators: qa_set_self_collision_hips / _thighs is on, and the actuator kernels exist without those rows only"); return QA_E_ARG;
+    }
+    float host[2 * QA_NUM_DOF];
+    for (int j = 0; j < QA_NUM_DOF; ++j) { host[j] = x->kp[j]; host[QA_NUM_DOF + j] = x->kd[j]; }
+    if (!s->act_tbl) HIP_TRY(hipMalloc((void **)&s->act_tbl, sizeof(host)));
+    HIP_TRY(hipDeviceSynchronize());                     // a launch in flight may still read the table
+    HIP_TRY(hipMemcpy(s->act_tbl, host, sizeof(host), hipMemcpyHostToDevice));
+    s->act_type = x->control_type;
     return QA_OK;
 }
 
@@ -1869,7 +1987,7 @@ int qa_env_step_dev(qa_sim *s, const float *actions, int32_t delay_steps, int64_
 int qa_env_physics_step(qa_sim *s, const float *actions, int32_t delay_steps, void *stream) {
     if (!s || !actions || delay_steps < 0 || delay_steps >= QA_ACTION_BUF_LEN) return QA_E_ARG;
     const int blocks = (s->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
-    k_levels[s->sc_level]->physics_step(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, make_step_args(s, actions, delay_steps, 0, nullptr, nullptr));
+    step_unit(s)->physics_step(s->cfg.terrain_type == 1, blocks, (hipStream_t)stream, make_step_args(s, actions, delay_steps, 0, nullptr, nullptr), act_args(s));
     HIP_TRY(hipGetLastError());
     return QA_OK;
 }
@@ -1997,4 +2115,4 @@ int qa_gae(const float *rewards, const float *values, const uint8_t *dones, cons
 }
 
 }  // extern "C"
-#endif   // QA_SCH_LEVEL == 0
+#endif   // QA_MAIN_UNIT

@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from quadrupedal_agility_amd import _capi, go2_limits
-from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import (class_to_dict, install_contact_sets, install_recovery_init, install_self_collision_hips, install_self_collision_thighs,
-                                                            make_extra_rewards, make_qa_config)
+from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import (class_to_dict, install_actuators, install_contact_sets, install_recovery_init, install_self_collision_hips,
+                                                            install_self_collision_thighs, make_extra_rewards, make_qa_config, resolve_pd_gains)
 
 KEY_BODY_NAMES = ["FL_foot", "FR_foot", "RL_foot", "RR_foot"]
 
@@ -79,6 +79,7 @@ class LeggedRobot:
         self.self_collision_thighs = install_self_collision_thighs(cfg, self.sim)
         self.recovery_init_prob = install_recovery_init(cfg, self.sim)            # launch arguments of the step: before anything records, too
         self.contact_class_masks = install_contact_sets(cfg, self.sim)
+        self.actuators = install_actuators(cfg, self.sim)                         # control type / per-joint gains: other kernels, so before anything records
         if self._mocap_table is not None:
             self.sim.set_mocap(*self._mocap_table)
         self._init_buffers()
@@ -190,8 +191,9 @@ class LeggedRobot:
         dev = self.device
         q0 = [self.cfg.init_state.default_joint_angles[n] for n in _capi.DOF_NAMES]
         self.default_dof_pos = torch.tensor(q0, dtype=torch.float, device=dev).unsqueeze(0)
-        self.p_gains = torch.full((12,), float(self.qcfg.kp), device=dev)
-        self.d_gains = torch.full((12,), float(self.qcfg.kd), device=dev)
+        kp, kd = resolve_pd_gains(self.cfg, report=False)                         # (12,) as in the reference (legged_robot.py:784-787, 844-858)
+        self.p_gains = torch.tensor(kp, dtype=torch.float, device=dev)
+        self.d_gains = torch.tensor(kd, dtype=torch.float, device=dev)
         # URDF limits (legged_robot.py:403-430), soft position limits
         self.dof_pos_limits = go2_limits.soft_dof_pos_limits(self.cfg.rewards.soft_dof_pos_limit, dev)
         self.dof_vel_limits = torch.tensor(go2_limits.DOF_VEL_LIMITS, device=dev)

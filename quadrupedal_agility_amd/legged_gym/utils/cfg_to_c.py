@@ -52,11 +52,8 @@ def make_qa_config(cfg, seed=1, sim_dt=None, terrain=None):
         c.reset_xy_jitter = 1.0          # custom_origins branch of _reset_root_states (legged_robot.py:622-625)
     else:
         raise ValueError("Terrain mesh type not recognised. Allowed types are [None, plane, heightfield, trimesh]")
-    if cfg.control.control_type != "P":
-        raise NotImplementedError("only control_type 'P' (legged_robot.py:563-570) is on the hot path")
-    kp = _gain(cfg.control.stiffness)
-    kd = _gain(cfg.control.damping)
-    c.kp, c.kd = kp, kd
+    # the one gain pair of the P law; any other actuator model travels in make_actuators' descriptor, and the kernels it selects do not read these
+    c.kp, c.kd = config_gains(cfg)
     c.action_scale = float(cfg.control.action_scale)
     c.hip_scale_reduction = float(getattr(cfg.control, "hip_scale_reduction", 1.0))
     c.clip_actions = float(cfg.normalization.clip_actions)
@@ -248,8 +245,71 @@ def make_extra_rewards(cfg, sim_dt=None):
     return ExtraRewards(scale_dt, getattr(cfg.rewards, "base_height_target", 0.0), getattr(cfg.rewards, "max_contact_force", 0.0), dt, scan)
 
 
-def _gain(table):
-    vals = {float(v) for k, v in table.items() if k in "joint" or "joint" in k}
-    if len(vals) != 1:
-        raise NotImplementedError("per-joint PD gains are not supported; Go2 uses one gain for every joint")
-    return vals.pop()
+CONTROL_TYPES = ("P", "V", "T")
+
+
+def _control_type(cfg):
+    control_type = cfg.control.control_type
+    if control_type not in CONTROL_TYPES:
+        raise NameError(f"Unknown controller type: {control_type}")                 # legged_robot.py:577
+    return control_type
+
+
+def resolve_pd_gains(cfg, report=True):
+    """The reference's p_gains / d_gains (bbc/legged_gym/envs/base/legged_robot.py:844-858), as two lists of twelve floats in _capi.DOF_NAMES order:
+    every key of control.stiffness that is a substring of the joint's name assigns both gains (stiffness[key], damping[key]), a later key
+    overwriting an earlier one; a joint no key matches gets 0 / 0, and for control types P and V the reference's one line about it is printed."""
+    stiffness, damping = cfg.control.stiffness, cfg.control.damping
+    control_type = _control_type(cfg)
+    kp, kd = [], []
+    for name in _capi.DOF_NAMES:
+        p, d, found = 0.0, 0.0, False
+        for key in stiffness.keys():
+            if key in name:
+                p, d, found = float(stiffness[key]), float(damping[key]), True
+        if not found and report and control_type in ("P", "V"):
+            print(f"PD gain of joint {name} were not defined, setting them to zero")
+        kp.append(p); kd.append(d)
+    return kp, kd
+
+
+def config_gains(cfg):
+    """qa_config.kp / kd: the gain pair of the first joint.  With make_actuators(cfg) None it is every joint's and the kernels read it; otherwise
+    the kernels qa_set_actuators selects take the table and ignore it."""
+    kp, kd = resolve_pd_gains(cfg, report=False)
+    return kp[0], kd[0]
+
+
+class Actuators:
+    """What qa_set_actuators (include/qa_sim_actuators.h) takes: the control type ('P', 'V' or 'T') and the twelve gain pairs."""
+
+    def __init__(self, control_type, kp, kd):
+        self.control_type, self.kp, self.kd = control_type, [float(v) for v in kp], [float(v) for v in kd]
+
+
+def make_actuators(cfg):
+    """The extension descriptor of the actuator model, next to make_qa_config's qa_config: None for control type P with the same gain pair on
+    all twelve joints (qa_config.kp / kd carry it and the step runs exactly as without the extension), a descriptor for V, T and per-joint
+    gains.  The kernels behind it exist without the opt-in self-collision rows only, so the combination is refused here."""
+    control_type = _control_type(cfg)
+    kp, kd = resolve_pd_gains(cfg)
+    if control_type == "P" and len(set(kp)) == 1 and len(set(kd)) == 1:
+        return None
+    if getattr(cfg.asset, "qa_self_collision_hips", False) or getattr(cfg.asset, "qa_self_collision_thighs", False):
+        raise ValueError(f"control.control_type {control_type!r} with gains {kp} / {kd} is an actuator model of qa_set_actuators, whose kernels are built "
+                         "without the calf-hip and calf-thigh rows: it cannot be combined with asset.qa_self_collision_hips / asset.qa_self_collision_thighs")
+    return Actuators(control_type, kp, kd)
+
+
+def install_actuators(cfg, sim):
+    """control.control_type / control.stiffness / control.damping -> qa_set_actuators (include/qa_sim_actuators.h) on the engine `sim`, for the
+    env classes of both trees.  With the P law and one gain pair nothing is called: that is what the kernels do on their own.  Call it after
+    the engine is created and before anything records a rollout: a recording bakes the kernel choice in.  Returns the descriptor in force."""
+    act = make_actuators(cfg)
+    if act is None:
+        return None
+    if not hasattr(sim, "set_actuators"):
+        raise NotImplementedError(f"control.control_type {act.control_type!r} / per-joint PD gains need the HIP engine (qa_set_actuators); this backend "
+                                  "computes the P law from one gain pair")
+    sim.set_actuators(act)
+    return act

@@ -110,6 +110,21 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
                 if "none" in names and len(names) > 1:
                     raise ValueError(f"--{flag} none stands alone: it empties the list")
                 setattr(env_cfg.asset, field, [] if names == ["none"] else list(names))
+        if getattr(args, "control_type", None) is not None:
+            env_cfg.control.control_type = args.control_type
+        gains = getattr(args, "pd_gains", None) or []
+        if gains:                                        # the flags replace both dicts, in the order given (a later key overwrites an earlier one)
+            stiffness, damping = {}, {}
+            for item in gains:
+                key, eq, value = item.partition("=")
+                kp, colon, kd = value.partition(":")
+                try:
+                    stiffness[key], damping[key] = float(kp), float(kd)
+                except ValueError:
+                    raise ValueError(f"--pd_gains {item}: expected KEY=KP:KD with numbers for KP and KD, e.g. hip=30:0.8") from None
+                if not (key and eq and colon):
+                    raise ValueError(f"--pd_gains {item}: expected KEY=KP:KD, e.g. hip=30:0.8")
+            env_cfg.control.stiffness, env_cfg.control.damping = stiffness, damping
         for item in getattr(args, "reward_scale", None) or []:
             name, eq, value = item.partition("=")
             if not hasattr(env_cfg.rewards.scales, name):
@@ -176,6 +191,10 @@ def get_args(argv=None):
                    help="asset.terminate_after_contacts_on = the NAMEs given (repeatable, replaces the list): base | hip | thigh | calf | foot; `none` alone empties it, so that only time-outs end an episode")
     p.add_argument("--penalize_on", action="append", default=[], metavar="NAME",
                    help="asset.penalize_contacts_on = the NAMEs given (repeatable, replaces the list): base | hip | thigh | calf | foot; `none` alone empties it")
+    p.add_argument("--control_type", choices=["P", "V", "T"], help="control.control_type: actions are position targets (P, the default), velocity targets (V) or scaled torques (T)")
+    p.add_argument("--pd_gains", action="append", default=[], metavar="KEY=KP:KD",
+                   help="control.stiffness[KEY] = KP, control.damping[KEY] = KD (repeatable, replaces both dicts): every joint whose name contains KEY, "
+                        "e.g. hip=30:0.8 thigh=40:1 calf=50:1.2; a joint no KEY matches gets 0 / 0, as in the reference")
     p.add_argument("--log_root", type=str, default="default")
     from quadrupedal_agility_amd.render import add_record_args
     add_record_args(p)                  # --record_frames [DIR] --record_envs --record_every --frame_size (play.py)

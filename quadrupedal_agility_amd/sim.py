@@ -8,7 +8,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi
+from . import _capi, _cdecl
 
 _TORCH_DT = {_capi.DTYPE_F32: torch.float32, _capi.DTYPE_I64: torch.int64, _capi.DTYPE_U8: torch.uint8,
              _capi.DTYPE_I32: torch.int32, _capi.DTYPE_I16: torch.int16, _capi.DTYPE_F64: torch.float64}
@@ -48,6 +48,7 @@ class QaSim:
         # include/qa_sim_reset.h: what the handle does until the setters below are called
         self.recovery_init_prob = 0.0
         self.contact_sets = (_capi.DEFAULT_TERMINATION_MASK, _capi.DEFAULT_PENALISED_MASK)
+        self.actuators = None            # include/qa_sim_actuators.h: the P law from cfg.kp / cfg.kd until set_actuators is called
 
     def reset_all(self):
         self.api.launch("reset_all", self.h, self.global_step, on=self.device)
@@ -137,6 +138,23 @@ class QaSim:
         counts for the collision penalty.  The kernels' defaults are base | hip and thigh | calf.  Call it before a rollout is recorded."""
         self.api.call("set_contact_sets", self.h, int(termination), int(penalised))
         self.contact_sets = (int(termination), int(penalised))
+
+    def set_actuators(self, actuators):
+        """qa_set_actuators (include/qa_sim_actuators.h): `actuators` is cfg_to_c.make_actuators' descriptor (control_type 'P' / 'V' / 'T', twelve
+        kp, twelve kd); None switches back to the kernels that read cfg.kp / cfg.kd.  The handle copies the gains to a device table of its own
+        (the C side allocates it once and frees it with the handle; nothing here has to stay alive).  It selects other kernel instantiations at
+        launch time, so call it before a rollout is recorded; refused while a self-collision level is on."""
+        if actuators is None:
+            self.api.call("set_actuators", self.h, None)
+            self.actuators = None
+            return
+        x = _cdecl.struct("qa_actuators")()
+        x.control_type = _cdecl.consts["QA_ACTUATOR_" + actuators.control_type]
+        for j in range(_capi.NUM_DOF):
+            x.kp[j], x.kd[j] = float(actuators.kp[j]), float(actuators.kd[j])
+        with torch.cuda.device(self.device):
+            self.api.call("set_actuators", self.h, C.byref(x))
+        self.actuators = actuators
 
     def step_dev(self, actions, delay, step_counter):
         """qa_env_step_dev: the step counter lives in device memory (graph-replayable)."""

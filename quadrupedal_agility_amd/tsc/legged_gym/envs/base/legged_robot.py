@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from quadrupedal_agility_amd import _capi, go2_limits
-from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import class_to_dict, install_self_collision_hips, install_self_collision_thighs
+from quadrupedal_agility_amd.legged_gym.utils.cfg_to_c import (class_to_dict, config_gains, install_actuators, install_self_collision_hips, install_self_collision_thighs,
+                                                            resolve_pd_gains)
 from quadrupedal_agility_amd.tsc.legged_gym.obstacle_curriculum import ObstacleCurriculum
 from quadrupedal_agility_amd.tsc.legged_gym.task_level import TaskLevelBookkeeping
 from quadrupedal_agility_amd.tsc.legged_gym.utils.obstacle import Obstacle
@@ -45,13 +46,7 @@ def make_qa_config(cfg, obstacle, seed=1):
     # see-saw = 1-DoF revolute plank with joint damping, bar / tyre = 1-DoF prismatic bodies under the reference's position drive
     # (QA_T_OBST_DESC / QA_T_OBST_STATE; :792-794, :812-823, :1411-1427); 0 = the static shapes of the height map (the r2 model)
     c.articulated_obstacles = int(bool(getattr(cfg.obstacle, "articulated", True)))
-    if cfg.control.control_type != "P":
-        raise NotImplementedError("only control_type 'P' is on the hot path")
-    kp = {float(v) for v in cfg.control.stiffness.values()}
-    kd = {float(v) for v in cfg.control.damping.values()}
-    if len(kp) != 1 or len(kd) != 1:
-        raise NotImplementedError("one PD gain for every joint")
-    c.kp, c.kd = kp.pop(), kd.pop()
+    c.kp, c.kd = config_gains(cfg)                       # the one-gain P law; anything else goes through install_actuators (qa_set_actuators)
     c.action_scale, c.hip_scale_reduction = float(cfg.control.action_scale), float(cfg.control.hip_scale_reduction)
     c.clip_actions = float(cfg.normalization.clip_actions)
     for i, name in enumerate(_capi.DOF_NAMES):
@@ -111,6 +106,7 @@ class LeggedRobot:
         self.device = str(backend.device)
         self.self_collision_hips = install_self_collision_hips(cfg, self.sim)      # before anything records a rollout: it selects the kernels
         self.self_collision_thighs = install_self_collision_thighs(cfg, self.sim)
+        self.actuators = install_actuators(cfg, self.sim)                         # control type / per-joint gains: other kernels, so before anything records
         dev = self.device
         t = self.sim.t
         # (a copy: on a CPU backend from_numpy would alias the course's own array, and the obstacle curriculum writes into this tensor)
@@ -140,6 +136,8 @@ class LeggedRobot:
         q0 = [cfg.init_state.default_joint_angles[n] for n in _capi.DOF_NAMES]
         self.default_dof_pos = torch.tensor(q0, dtype=torch.float, device=dev).unsqueeze(0)
         self.default_dof_pos_all = self.default_dof_pos.clone()
+        kp, kd = resolve_pd_gains(cfg, report=False)                              # (12,) as in the reference (:1025-1026, :1073-1087)
+        self.p_gains, self.d_gains = torch.tensor(kp, dtype=torch.float, device=dev), torch.tensor(kd, dtype=torch.float, device=dev)
         names = _capi.BODY_NAMES
         self.feet_indices = torch.tensor([i for i, n in enumerate(names) if cfg.asset.foot_name in n], device=dev)
         self.penalised_contact_indices = torch.tensor([i for i, n in enumerate(names) if any(k in n for k in cfg.asset.penalize_contacts_on)], device=dev)

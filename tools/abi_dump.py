@@ -14,7 +14,8 @@ classes and its constants), so the same file describes any commit's binding, how
   constants   every public int, float, str, list, tuple and dict (with the container's type: a tuple is not a list)
 LIB_PATH is left out: it is where this checkout lies, not part of the ABI.
 The headers of _capi._RECORDED_APART have records of their own beside it, in the same form (dump_apart): their entry points, with the header's
-name as the list, and their structs.  --write and --check go over all of them."""
+name as the list, and their structs.  _capi._RECORDED_APART_ENGINE names the env engine's headers recorded the same way (dump_apart(that table));
+their entry points are EXTENSION_SYMBOLS too, and dump() leaves them to their own record.  --write and --check go over all of them."""
 import ctypes as C
 import json
 import os
@@ -53,10 +54,11 @@ def struct_record(cls):
 
 def dump():
     sys.path.insert(0, ROOT)
-    from quadrupedal_agility_amd import _capi
+    from quadrupedal_agility_amd import _capi, _cdecl
     lib = _capi.load_library()
     functions = {}
-    symbols = [(name, which) for which in ("ABI_SYMBOLS", "EXTENSION_SYMBOLS") for name in getattr(_capi, which)]
+    apart = {name for h, name, _, _ in _cdecl.prototypes if h in getattr(_capi, "_RECORDED_APART_ENGINE", {})}
+    symbols = [(name, which) for which in ("ABI_SYMBOLS", "EXTENSION_SYMBOLS") for name in getattr(_capi, which) if name not in apart]
     assert len(set(name for name, _ in symbols)) == len(symbols), "a symbol is listed twice"
     for name, which in symbols:
         f = getattr(lib, "qa_" + name)
@@ -77,13 +79,14 @@ def dump():
     return {"functions": functions, "structs": structs, "constants": constants}
 
 
-def dump_apart():
-    """{record file under tests/golden: dump} for the headers of _capi._RECORDED_APART; a struct qa_some_name is recorded as QaSomeName"""
+def dump_apart(table=None):
+    """{record file under tests/golden: dump} for the headers of `table` (default _capi._RECORDED_APART; the other one is
+    _capi._RECORDED_APART_ENGINE); a struct qa_some_name is recorded as QaSomeName"""
     sys.path.insert(0, ROOT)
     from quadrupedal_agility_amd import _capi, _cdecl
     lib = _capi.load_library()
     out = {}
-    for header, (record, cnames) in _capi._RECORDED_APART.items():
+    for header, (record, cnames) in (_capi._RECORDED_APART if table is None else table).items():
         functions = {}
         for h, name, _, _ in _cdecl.prototypes:
             if h == header:
@@ -117,7 +120,9 @@ def differences(a, b, path=""):
 
 
 if __name__ == "__main__":
-    d, apart = dump(), dump_apart()
+    sys.path.insert(0, ROOT)
+    from quadrupedal_agility_amd import _capi as _c
+    d, apart = dump(), {**dump_apart(), **dump_apart(_c._RECORDED_APART_ENGINE)}
     files = [(GOLDEN, d)] + [(os.path.join(os.path.dirname(GOLDEN), record), rec) for record, rec in apart.items()]
     if "--write" in sys.argv:
         for path, rec in files:

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Dev tool: do two trees compile the same device code?  Needs hipcc, no GPU.
 
-  python tools/device_listing_diff.py TREE_A TREE_B qa_sim.hip qa_sim_selfcol.hip ... [--rename OLD=NEW ...] [--jobs N]
+  python tools/device_listing_diff.py TREE_A TREE_B qa_sim.hip qa_sim_selfcol.hip ... [--rename OLD=NEW ...] [--rename-re PATTERN=REPL ...] [--jobs N]
 
 Each source (a name under quadrupedal_agility_amd/csrc) is compiled in both trees with the flags HIP_SOURCES (__graft_entry__.py of the tree
 this tool lives in) gives it, plus -S --cuda-device-only, and the two listings are compared kernel symbol by kernel symbol: from the kernel's
 label to its .end_amdhsa_kernel, i.e. the instructions and the kernel descriptor.  Before the comparison the `;` comments go, local labels
 (.L...) are numbered by first appearance inside the kernel (their numbers depend on the kernel's position in the file, their structure does
-not), the __hip_cuid_* symbol loses its hash, and --rename OLD=NEW rewrites a symbol of TREE_A that TREE_B names differently.  The order of
+not), the __hip_cuid_* symbol loses its hash, and --rename OLD=NEW rewrites a symbol of TREE_A that TREE_B names differently (--rename-re: a
+regular expression and its replacement, for a template's whole family of mangled names).  The order of
 the kernels in a file is not compared.  Prints the symbols only one tree has, the symbols whose text differs, and the totals; exit status 1
 if there is any of either."""
 import argparse
@@ -35,7 +36,7 @@ def listing(tree, src, out):
 def kernels(text, renames):
     """{kernel symbol: normalised lines from its label to .end_amdhsa_kernel}"""
     for old, new in renames:
-        text = re.sub(r"\b%s\b" % re.escape(old), new, text)
+        text = old.sub(new, text) if hasattr(old, "sub") else re.sub(r"\b%s\b" % re.escape(old), new, text)
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid", text)
     lines = text.split("\n")
     label = {m.group(1): i for i, m in ((i, re.match(r"([A-Za-z_$][\w$.]*):", ln)) for i, ln in enumerate(lines)) if m}
@@ -60,12 +61,14 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("tree_a"); ap.add_argument("tree_b"); ap.add_argument("sources", nargs="+")
     ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="a symbol of TREE_A that TREE_B names NEW")
+    ap.add_argument("--rename-re", action="append", default=[], metavar="PATTERN=REPL",
+                    help="the same for a family of symbols: a regular expression over TREE_A's listing and its replacement (a template gained a parameter)")
     ap.add_argument("--jobs", type=int, default=min(6, os.cpu_count() or 1))
     a = ap.parse_args()
-    renames = [tuple(r.split("=", 1)) for r in a.rename]
+    renames = [tuple(r.split("=", 1)) for r in a.rename] + [(re.compile(p), r) for p, r in (x.split("=", 1) for x in a.rename_re)]
     print(f"A = {a.tree_a}\nB = {a.tree_b}\nflags: {' '.join(BASE)} + HIP_SOURCES' + -S --cuda-device-only")
     for old, new in renames:
-        print(f"renamed in A: {old} -> {new}")
+        print(f"renamed in A: {getattr(old, 'pattern', old)} -> {new}")
     bad = 0
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(a.jobs) as pool:
         jobs = {(t, s): pool.submit(listing, tree, s, os.path.join(tmp, f"{t}_{s}.s"))
