@@ -83,6 +83,39 @@ def _node(cfg, dotted):
     return cfg
 
 
+def _terrain_course_from_args(env_cfg, args):
+    """--terrain_proportions / --terrain_selected: which tile kinds the height-field course is built from (utils/terrain.py)"""
+    props, selected = getattr(args, "terrain_proportions", None), getattr(args, "terrain_selected", None)
+    for flag, value in (("terrain_proportions", props), ("terrain_selected", selected)):
+        if value is not None and env_cfg.terrain.mesh_type not in ("heightfield", "trimesh"):
+            raise ValueError(f"--{flag} {value}: needs --terrain trimesh or --terrain heightfield (terrain.mesh_type is {env_cfg.terrain.mesh_type!r})")
+    if props is not None:
+        try:
+            shares = [float(x) for x in props.split(",")]
+        except ValueError:
+            shares = []
+        if not 5 <= len(shares) <= 7 or any(not 0.0 <= s < float("inf") for s in shares):
+            raise ValueError(f"--terrain_proportions {props}: expected five to seven non-negative numbers separated by commas, e.g. 0.1,0.1,0.35,0.25,0.2")
+        env_cfg.terrain.terrain_proportions = shares
+    if selected is not None:
+        from .terrain import GENERATORS
+        name, _, rest = selected.partition(":")
+        if (name[len("terrain_utils."):] if name.startswith("terrain_utils.") else name) not in GENERATORS:
+            raise ValueError(f"--terrain_selected {selected}: expected NAME[:KEY=VALUE,...] with NAME one of {', '.join(GENERATORS)}")
+        kwargs = {"type": name}
+        for item in filter(None, rest.split(",")):
+            key, eq, value = item.partition("=")
+            try:
+                number = float(value)
+            except ValueError:
+                number = None
+            if not (key and eq) or number is None or not np.isfinite(number) or key == "type":
+                raise ValueError(f"--terrain_selected {selected}: expected NAME[:KEY=VALUE,...] with a number for every VALUE, "
+                                 "e.g. pyramid_stairs_terrain:step_width=0.31,step_height=0.15,platform_size=3")
+            kwargs[key] = int(value) if value.strip().lstrip("+-").isdigit() else number      # counts (num_rects=20) stay integers
+        env_cfg.terrain.selected, env_cfg.terrain.terrain_kwargs = True, kwargs
+
+
 def update_cfg_from_args(env_cfg, cfg_train, args):
     """Same override table as helpers.py:102-168."""
     if env_cfg is not None:
@@ -94,6 +127,7 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             env_cfg.terrain.mesh_type = args.terrain
         if getattr(args, "terrain_curriculum", False):
             env_cfg.terrain.curriculum = True
+        _terrain_course_from_args(env_cfg, args)
         if getattr(args, "self_collision_hips", False):
             env_cfg.asset.qa_self_collision_hips = True
         if getattr(args, "self_collision_thighs", False):
@@ -180,6 +214,10 @@ def get_args(argv=None):
     p.add_argument("--physics_engine", default="qa")
     p.add_argument("--terrain", type=str, default=None, help="override terrain.mesh_type: plane | heightfield | trimesh")
     p.add_argument("--terrain_curriculum", action="store_true", help="terrain.curriculum = True: resetting envs move between the course's difficulty rows (heightfield | trimesh)")
+    p.add_argument("--terrain_proportions", type=str, metavar="P0,P1,...", help="terrain.terrain_proportions: five to seven shares of the course's tile kinds -- smooth slope, rough slope, stairs down, stairs up, "
+                   "discrete obstacles[, stepping stones[, gaps]], the rest pits -- e.g. 0.1,0.1,0.35,0.25,0.2 (heightfield | trimesh)")
+    p.add_argument("--terrain_selected", type=str, metavar="NAME[:KEY=VALUE,...]", help="terrain.selected = True: every tile from one generator of utils/terrain.py, "
+                   "e.g. pyramid_stairs_terrain:step_width=0.31,step_height=0.15,platform_size=3 (heightfield | trimesh)")
     p.add_argument("--self_collision_hips", action="store_true", help="asset.qa_self_collision_hips = True: a front calf collides with the rear hip of its side (a hip contact ends the episode, as in the reference)")
     p.add_argument("--self_collision_thighs", action="store_true", help="asset.qa_self_collision_thighs = True: each calf of a front / rear pair of legs collides with the other leg's thigh (the collision penalty counts it; pass --self_collision_hips too)")
     p.add_argument("--reward_scale", action="append", default=[], metavar="NAME=VALUE",
